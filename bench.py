@@ -11,6 +11,12 @@ random initial mean; fp32 compute (the reference runs CMA-ES in float32).
 
 Usage: ``python bench.py [--gpus N] [--steps K] [--warmup W]``; with N > 1 the
 driver launches it under ``torch.distributed.run`` (one rank per GPU).
+
+A plain run sets up, warms up, times the K generations and prints the result line.
+``--full`` adds what takes work of its own: the per-phase breakdown (``--phase-steps``
+eager generations after the timed loop, ``phases_ms_eager``) and the eigensolver
+statistics of the timed generations (``eigh_stats``).  ``--dump-outputs DIR`` writes the
+state returned by the last timed generation as ``DIR/<field>.npy`` (see ``dump_outputs``).
 """
 from __future__ import annotations
 
@@ -21,6 +27,41 @@ import sys
 import time
 
 import torch
+
+
+DUMP_ARRAY_BYTES = 12 << 20  # per array: the CMA-ES state has four large fields (C, B, invsqrtC, population), 64 MB allowed in all
+
+
+def _tensor_leaves(state, prefix=""):
+    """(dotted name, tensor) of every tensor field of a State tree, children included."""
+    for k in state.keys():
+        v = state[k]
+        if isinstance(v, torch.Tensor):
+            yield prefix + k, v
+    for name, child in state._child_states.items():
+        yield from _tensor_leaves(child, prefix + name + ".")
+
+
+def dump_outputs(state, out_dir):
+    """Write every tensor of the workflow state a caller of ``wf.step`` receives (mean, sigma,
+    C, B, D, the evolution paths, the sampled population, ...) as ``out_dir/<name>.npy``.
+
+    float32 / float64 fields keep their dtype, integer fields (RNG key, counters) are stored
+    exactly as float64.  An array above ``DUMP_ARRAY_BYTES`` (the population) is cut down to
+    a fixed sample of its rows: the first k indices, sorted, of a permutation seeded with 0,
+    which depends on the shape alone, so two runs with the same arguments keep the same rows."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in _tensor_leaves(state):
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64)
+        if t.dim() and t.numel() * t.element_size() > DUMP_ARRAY_BYTES:
+            k = max(DUMP_ARRAY_BYTES // (t.element_size() * (t.numel() // t.shape[0])), 1)
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:k].sort().values
+            t = t[rows.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
 
 
 def main():
@@ -34,7 +75,13 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--profile-phases", action="store_true")
     ap.add_argument("--force-dist", action="store_true", help="run the distributed (sharded + RCCL) path even on one rank")
-    ap.add_argument("--phase-steps", type=int, default=3, help="eager generations timed per phase after the timed loop (0: off)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the eager per-phase breakdown (--phase-steps) "
+                         "and the eigensolver statistics of the timed generations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state returned by the last timed generation as DIR/<field>.npy")
+    ap.add_argument("--phase-steps", type=int, default=3,
+                    help="with --full: eager generations timed per phase after the timed loop (0: off)")
     ap.add_argument("--simulate-rank", type=int, default=None,
                     help="time rank R's share of a --world N step on this one GPU (collectives replaced by same-size local ops)")
     ap.add_argument("--world", type=int, default=8, help="world size simulated by --simulate-rank")
@@ -123,8 +170,9 @@ def main():
         # every graph variant the timed generations replay is captured here, not inside the timing
         state = wf.prepare_graphs(state, args.steps + 1)
     sync()
-    eigh_mod.HISTORY.clear()
-    dev_counts = sbr_device.snapshot_counts()  # device-mode solves: per-solve ring read after timing
+    if args.full:
+        eigh_mod.HISTORY.clear()
+        dev_counts = sbr_device.snapshot_counts()  # device-mode solves: per-solve ring read after timing
     if sim_ctx is not None:
         sim_ctx.counters.reset()  # wire accounting of the timed generations only
     t0 = time.perf_counter()
@@ -133,12 +181,16 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     wire = sim_ctx.counters.summary(args.steps, sim_ctx.wire, args.world, graph=use_graph) if sim_ctx is not None else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(state, args.dump_outputs)  # before the eager phase generations below move the state on
+    hist, dev_hist = [], None
+    if args.full:
+        hist = list(eigh_mod.HISTORY)  # decompositions of the timed generations only (host mode)
+        dev_hist = sbr_device.histories_since(dev_counts)  # [off_rel, 0, iterations, fallback] (device mode)
     # per-phase breakdown (outside the timed region): a few eager generations with
     # stream-ordered hipEvent timers; "tell" includes "eigh" (and "all_reduce" when sharded)
-    hist = list(eigh_mod.HISTORY)  # decompositions of the timed generations only (host mode)
-    dev_hist = sbr_device.histories_since(dev_counts)  # [off_rel, 0, iterations, fallback] (device mode)
     phases = None
-    if args.phase_steps > 0:
+    if args.full and args.phase_steps > 0:
         from evoxmi.utils.profiling import PhaseTimer
 
         timer = PhaseTimer(device)
@@ -198,9 +250,9 @@ def main():
         if phases:
             out["phases_ms_eager"] = phases
         if args.monitor:
-            hist = monitors[0].get_history()
-            out["monitor"] = {"type": "EvalMonitor", "mode": args.monitor, "generations_recorded": len(hist),
-                              "host_side": bool(hist) and not hist[-1].is_cuda,
+            mon_hist = monitors[0].get_history()
+            out["monitor"] = {"type": "EvalMonitor", "mode": args.monitor, "generations_recorded": len(mon_hist),
+                              "host_side": bool(mon_hist) and not mon_hist[-1].is_cuda,
                               "best_fitness": float(monitors[0].get_best_fitness())}
         if sim:
             # one rank's share of an N-GPU step (the driver's --gpus 1 headline never sets this)
@@ -218,7 +270,7 @@ def main():
                 out["simulated"]["replicated_ms_eager"] = rep
                 out["simulated"]["sharded_ms_eager"] = round(phases.get("ask", 0.0) + phases.get("evaluate", 0.0) +
                                                              phases.get("tell", 0.0) - rep, 4)
-        if dev_hist.shape[0]:
+        if dev_hist is not None and dev_hist.shape[0]:
             # every timed generation's decomposition (device-controlled schedule, read back
             # once after the timed loop): relative off-norm ‖offdiag(BᵀCB)‖/‖diag‖
             out["eigh_stats"] = {

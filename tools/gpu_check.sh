@@ -13,8 +13,9 @@ echo "== smoke"
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 || { tail -30 gpurun_out/smoke.log; exit 1; }
 tail -2 gpurun_out/smoke.log
 echo "== bench"
-timeout -k 10 300 python bench.py --steps ${STEPS:-20} --warmup ${WARMUP:-3} ${BENCH_ARGS} > gpurun_out/bench.log 2>&1 || { tail -30 gpurun_out/bench.log; exit 1; }
-cat gpurun_out/bench.log | tail -3
+BENCH_LOG=$(mktemp)  # --full: the phase breakdown and the eigensolver statistics are read from this line
+timeout -k 10 300 python bench.py --full --steps ${STEPS:-20} --warmup ${WARMUP:-3} ${BENCH_ARGS} > "$BENCH_LOG" 2>&1 || { tail -30 "$BENCH_LOG"; exit 1; }
+tail -3 "$BENCH_LOG"
 if [ -n "$PROFILE" ]; then
   echo "== rocprof"
   cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/gpurun_out/prof -o run --output-format csv -- python3 $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 2 ${BENCH_ARGS} > $GRAFT_REPO_ROOT/gpurun_out/prof.log 2>&1 || { tail -20 $GRAFT_REPO_ROOT/gpurun_out/prof.log; exit 1; }
