@@ -62,6 +62,7 @@ def _worker(rank, world, port, kind, gens, out, seed=3):
     out[rank] = alg[_field(kind)].cpu()
     if kind in ("cmaes", "flagship"):
         out[("sigma", rank)] = alg["sigma"].cpu()
+        out[("C", rank)] = alg["C"].cpu()
     destroy()
 
 
@@ -81,6 +82,9 @@ def test_sharded_two_ranks_on_gpu_match_single_process(kind, gens):
     out = mgr.dict()
     mp.spawn(_worker, args=(2, _free_port(), kind, gens, out), nprocs=2, join=True)
     assert torch.equal(out[0], out[1])  # replicas stay bit-identical
+    if kind in ("cmaes", "flagship"):
+        # the covariance too: a wrong element of the packed all-reduce reaches the mean only a generation later
+        assert torch.equal(out[("C", 0)], out[("C", 1)])
     if kind == "cmaes" and gens > 1:
         return
     if kind == "flagship":
@@ -119,6 +123,7 @@ def test_sharded_cmaes_tracks_single_process_over_many_generations():
         out = mgr.dict()
         mp.spawn(_worker, args=(2, _free_port(), "cmaes", gens, out, seed), nprocs=2, join=True)
         assert torch.equal(out[0], out[1]) and torch.equal(out[("sigma", 0)], out[("sigma", 1)])
+        assert torch.equal(out[("C", 0)], out[("C", 1)])
         f_ref = float(wf.problem.evaluate(None, ref_mean[None, :])[0][0])
         f_sh = float(wf.problem.evaluate(None, out[0].cuda()[None, :])[0][0])
         assert f_ref < f0 and f_sh < f0

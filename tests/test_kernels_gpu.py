@@ -765,11 +765,15 @@ def test_cmaes_fused_epilogue_matches_torch_ops(d):
     dm = 0.1 * torch.randn(d, device="cuda", generator=g)
     Y = torch.randn(alg.mu, d, device="cuda", generator=g)
     S = (Y.T * alg.weights) @ Y
+    # the fused paths kernel advances the counters itself and uses count_iter + 1 for this
+    # generation; the torch side takes the count as it finds it, so it gets the advanced one
+    assert alg._counts_in_tell(a)
     outs = []
     for fused in (0, 1):
         with config.override(cma_fused=fused):
-            outs.append(alg._finish_tell(a, dm, S))
+            outs.append(alg._finish_tell(a if fused else a.update(count_iter=a.count_iter + 1), dm, S))
     r, f = outs
+    assert int(f.count_iter) == int(r.count_iter) == int(a.count_iter) + 1
     for k in ("mean", "sigma", "ps", "pc"):
         assert torch.allclose(f[k], r[k], rtol=1e-5, atol=1e-6), k
     assert torch.allclose(f.C, r.C, rtol=1e-5, atol=1e-6)
