@@ -1486,6 +1486,26 @@ at::Tensor nsga_select(const at::Tensor& rank, const at::Tensor& f, int64_t N, i
   return keep;
 }
 
+at::Tensor nsga3_niche_select(const at::Tensor& rank, const at::Tensor& last_rank, const at::Tensor& group, const at::Tensor& group_dist,
+                              const at::Tensor& key, int64_t N, int64_t R) {
+  CHECK_DEV(rank); CHECK_CONTIG(rank); CHECK_DEV(last_rank); CHECK_DEV(group); CHECK_CONTIG(group);
+  CHECK_DEV(group_dist); CHECK_F32(group_dist); CHECK_CONTIG(group_dist);
+  check_key(key);
+  const int64_t n = rank.numel();
+  TORCH_CHECK(rank.scalar_type() == at::kInt && rank.dim() == 1, "nsga3_niche_select: rank int32 (n,)");
+  TORCH_CHECK(last_rank.scalar_type() == at::kInt && last_rank.numel() == 1, "nsga3_niche_select: last_rank is one int32 device word");
+  TORCH_CHECK(group.scalar_type() == at::kLong && group.dim() == 1 && group.numel() == n, "nsga3_niche_select: group int64 (n,)");
+  TORCH_CHECK(group_dist.dim() == 1 && group_dist.numel() == n, "nsga3_niche_select: group_dist float32 (n,)");
+  TORCH_CHECK(n >= 1 && n <= 8192, "nsga3_niche_select: 1 <= n <= 8192");
+  TORCH_CHECK(R >= 1 && R <= 8192, "nsga3_niche_select: 1 <= R <= 8192");
+  TORCH_CHECK(N >= 1 && N <= n, "nsga3_niche_select: need 1 <= N <= n");
+  c10::DeviceGuard g(rank.device());
+  auto idx = at::empty({N}, rank.options().dtype(at::kLong));
+  evx_nsga3_niche_select(rank.data_ptr<int>(), last_rank.data_ptr<int>(), group.data_ptr<int64_t>(), group_dist.data_ptr<float>(),
+                         key.data_ptr<int64_t>(), (int)n, (int)N, (int)R, idx.data_ptr<int64_t>(), cur_stream());
+  return idx;
+}
+
 }  // namespace
 
 // OpenES gradient with Philox-regenerated noise: g[j] = Σ_i w[i] ε(row0 + i, j)
@@ -1612,6 +1632,7 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("cma_cov_pad(Tensor C, Tensor S, Tensor pc, Tensor a, float c1, float cmu, Tensor Bprev, int np, Tensor? Cn_out=None, bool want_bp=True) -> Tensor[]");
   m.def("cma_eig_out(Tensor Bp, Tensor w, int d, Tensor? B_out=None, Tensor? B_alt=None, Tensor? keep=None) -> Tensor[]");
   m.def("nsga_select(Tensor rank, Tensor f, int N, int mask_pos) -> Tensor");
+  m.def("nsga3_niche_select(Tensor rank, Tensor last_rank, Tensor group, Tensor group_dist, Tensor key, int N, int R) -> Tensor");
   m.def("moead_parents(Tensor nb, Tensor key, int row0=0, int rows=0) -> Tensor[]");
   m.def("moead_variation(Tensor pop, Tensor p0, Tensor p1, Tensor kx, Tensor km, Tensor lb, Tensor ub, float pro_c, float dis_c, float pro_m, float dis_m, int nm, int row0=0, int rows=0, Tensor? win=None, Tensor(a!)? out=None) -> Tensor");
   m.def("moead_halo_replace(Tensor(a!) obj, Tensor off_obj, Tensor W, Tensor z, Tensor zmax, Tensor rowptr, Tensor owner, Tensor slots, int func, Tensor(b!) win_h) -> ()");
@@ -1701,6 +1722,7 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("cma_cov_pad", &cma_cov_pad);
   m.impl("cma_eig_out", &cma_eig_out);
   m.impl("nsga_select", &nsga_select);
+  m.impl("nsga3_niche_select", &nsga3_niche_select);
   m.impl("moead_parents", &moead_parents);
   m.impl("moead_variation", &moead_variation);
   m.impl("moead_replace", &moead_replace);

@@ -240,6 +240,9 @@ void evx_cma_eig_out(const float* Bp, const float* w, int d, int np, float* B, f
 
 // nsga_select.hip
 void evx_nsga_select(const int32_t* rank, const float* f, int n, int m, int N, int mask_pos, int64_t* keep, hipStream_t s);
+// nsga3_select.hip: NSGA-III niche-preserving selection (n ≤ 8192, R ≤ 8192), idx (N,) ascending rows
+void evx_nsga3_niche_select(const int32_t* rank, const int32_t* last_rank, const int64_t* group, const float* group_dist,
+                            const int64_t* key, int n, int N, int R, int64_t* idx, hipStream_t s);
 // sorted-block refinement of a warm-started eigendecomposition (eigh_sbr.hip, evoxmi/ops/sbr.py)
 int evx_sbr_nblocks(int n, int off);
 int evx_sbr_stat_parts();

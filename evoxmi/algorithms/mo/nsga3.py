@@ -12,6 +12,11 @@ exactly the lexicographic order of the pairs (ρ_j + k, j) over niches j and the
 k-th last-front member, so the loop is replaced by one sort: each candidate gets its
 within-niche position k (closest first for empty niches, random otherwise) and the K
 smallest (ρ_j + k, j) are kept.  Same distribution, no data-dependent loop.
+
+That selection is ``ops.nds.nsga3_survivors``: one launch of ``nsga3_select.hip`` on the
+device (merged population ≤ 8192 rows, ≤ 8192 reference points), the same steps in
+fixed-shape torch on the CPU and above those caps.  Neither reads anything on the host, so
+a whole generation is captured into one hipGraph (``StdWorkflow(..., graph=True)``).
 """
 from __future__ import annotations
 
@@ -22,6 +27,7 @@ from ...operators import selection
 from ...operators.sampling import UniformSampling
 from ...operators.selection.non_dominate import non_dominated_sort
 from ...ops import random as rnd
+from ...ops.nds import nsga3_survivors
 from ...utils.common import cos_dist
 from .common import MOAlgorithm
 
@@ -63,34 +69,7 @@ class NSGA3(MOAlgorithm):
         cosine = cos_dist(Fn, self.ref).clamp(-1, 1)
         dist = torch.linalg.norm(Fn, dim=-1, keepdim=True) * torch.sqrt(torch.clamp(1 - cosine**2, min=0))
         group_dist, group = dist.min(1)
-        R = self.ref.shape[0]
-        front = rank < last_rank
-        last = rank == last_rank
-        rho = torch.bincount(group[front], minlength=R)
-        K = N - int(front.sum())
-        cand = torch.nonzero(last).flatten()
-        g = group[cand]
-        u = rnd.uniform(state.key, (cand.shape[0],)).to(Fn.device)
-        # the closest member of an empty niche goes first
-        gd = group_dist[cand]
-        big = torch.full((R,), float("inf"), device=Fn.device).scatter_reduce(0, g, gd, "amin")
-        first = (rho[g] == 0) & (gd == big[g])
-        key_in = torch.where(first, torch.full_like(u, -1.0), u)
-        o = lexsort_pair(g, key_in)  # candidates ordered by (niche, key)
-        g_o = g[o]
-        starts = torch.searchsorted(g_o, g_o, right=False)
-        k = torch.arange(g_o.shape[0], device=Fn.device) - starts
-        level = rho[g_o] + k
-        pick = lexsort_pair(level, g_o.to(torch.float32))[:K]
-        chosen = cand[o[pick]]
-        keep = front.clone()
-        keep[chosen] = True
-        idx = torch.nonzero(keep).flatten()[:N]
+        # niche-preserving selection from the last front: nsga3_select.hip on the device
+        idx = nsga3_survivors(rank, last_rank, group, group_dist, state.key, N, self.ref.shape[0])
         key, _ = rnd.split(state.key)
         return state.update(population=merged_pop[idx], fitness=merged_fit[idx], key=key)
-
-
-def lexsort_pair(primary, secondary):
-    """Order by (primary, secondary) ascending, stable."""
-    o = torch.argsort(secondary, stable=True)
-    return o[torch.argsort(primary[o], stable=True)]
