@@ -1506,6 +1506,34 @@ at::Tensor nsga3_niche_select(const at::Tensor& rank, const at::Tensor& last_ran
   return idx;
 }
 
+at::Tensor sra_rank(const at::Tensor& I1, const at::Tensor& I2, const at::Tensor& u, const at::Tensor& pc) {
+  CHECK_DEV(I1); CHECK_F32(I1); CHECK_CONTIG(I1); CHECK_DEV(I2); CHECK_F32(I2); CHECK_CONTIG(I2);
+  CHECK_DEV(u); CHECK_F32(u); CHECK_CONTIG(u); CHECK_DEV(pc); CHECK_F32(pc);
+  const int64_t n = I1.numel();
+  TORCH_CHECK(I1.dim() == 1 && I2.dim() == 1 && I2.numel() == n, "sra_rank: I1, I2 float32 (n,)");
+  TORCH_CHECK(u.numel() >= std::max<int64_t>(n - 1, 0), "sra_rank: u needs at least n - 1 entries");
+  TORCH_CHECK(pc.numel() == 1, "sra_rank: pc is one float32 device word");
+  TORCH_CHECK(n <= evx_sra_rank_max_n(), "sra_rank: n <= ", evx_sra_rank_max_n());
+  TORCH_CHECK(I2.device() == I1.device() && u.device() == I1.device() && pc.device() == I1.device(), "sra_rank: one device");
+  c10::DeviceGuard g(I1.device());
+  auto rank = at::empty({n}, I1.options().dtype(at::kLong));
+  evx_sra_rank(I1.data_ptr<float>(), I2.data_ptr<float>(), u.data_ptr<float>(), pc.data_ptr<float>(), (int)n, rank.data_ptr<int64_t>(),
+               cur_stream());
+  return rank;
+}
+
+std::vector<at::Tensor> sra_indicators(const at::Tensor& obj) {
+  CHECK_DEV(obj); CHECK_F32(obj); CHECK_CONTIG(obj);
+  TORCH_CHECK(obj.dim() == 2, "sra_indicators: obj float32 (n, m)");
+  const int64_t n = obj.size(0), m = obj.size(1);
+  TORCH_CHECK(m >= 1 && m <= evx_sra_indicators_max_m(), "sra_indicators: 1 <= m <= ", evx_sra_indicators_max_m());
+  TORCH_CHECK(n <= (1 << 24), "sra_indicators: n <= 2^24");
+  c10::DeviceGuard g(obj.device());
+  auto I1 = at::empty({n}, obj.options()), I2 = at::empty({n}, obj.options());
+  evx_sra_indicators(obj.data_ptr<float>(), (int)n, (int)m, I1.data_ptr<float>(), I2.data_ptr<float>(), cur_stream());
+  return {I1, I2};
+}
+
 }  // namespace
 
 // OpenES gradient with Philox-regenerated noise: g[j] = Σ_i w[i] ε(row0 + i, j)
@@ -1633,6 +1661,8 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("cma_eig_out(Tensor Bp, Tensor w, int d, Tensor? B_out=None, Tensor? B_alt=None, Tensor? keep=None) -> Tensor[]");
   m.def("nsga_select(Tensor rank, Tensor f, int N, int mask_pos) -> Tensor");
   m.def("nsga3_niche_select(Tensor rank, Tensor last_rank, Tensor group, Tensor group_dist, Tensor key, int N, int R) -> Tensor");
+  m.def("sra_rank(Tensor I1, Tensor I2, Tensor u, Tensor pc) -> Tensor");
+  m.def("sra_indicators(Tensor obj) -> Tensor[]");
   m.def("moead_parents(Tensor nb, Tensor key, int row0=0, int rows=0) -> Tensor[]");
   m.def("moead_variation(Tensor pop, Tensor p0, Tensor p1, Tensor kx, Tensor km, Tensor lb, Tensor ub, float pro_c, float dis_c, float pro_m, float dis_m, int nm, int row0=0, int rows=0, Tensor? win=None, Tensor(a!)? out=None) -> Tensor");
   m.def("moead_halo_replace(Tensor(a!) obj, Tensor off_obj, Tensor W, Tensor z, Tensor zmax, Tensor rowptr, Tensor owner, Tensor slots, int func, Tensor(b!) win_h) -> ()");
@@ -1723,6 +1753,8 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("cma_eig_out", &cma_eig_out);
   m.impl("nsga_select", &nsga_select);
   m.impl("nsga3_niche_select", &nsga3_niche_select);
+  m.impl("sra_rank", &sra_rank);
+  m.impl("sra_indicators", &sra_indicators);
   m.impl("moead_parents", &moead_parents);
   m.impl("moead_variation", &moead_variation);
   m.impl("moead_replace", &moead_replace);

@@ -1,8 +1,10 @@
 // Host-side stochastic ranking (Runarsson & Yao 2000) used by SRA (reference
 // algorithms/mo/sra.py:22-85): bubble-sort sweeps in which each adjacent comparison uses
 // indicator I1 with probability pc (else I2), larger value first, stopping after
-// ⌈n/2⌉ sweeps or a sweep without swaps.  Inherently sequential and tiny (n ≤ 2N), so it
-// runs on the host; header-only so the sanitizer harness (tests/native) builds it alone.
+// ⌈n/2⌉ sweeps or a sweep without swaps.  The sequential statement of the sort: the CPU path
+// of evoxmi/ops/sra.py and the oracle of the device kernel, which runs the same sweeps
+// pipelined (csrc/kernels/sra_select.hip); header-only so the sanitizer harness (tests/native)
+// builds it alone.
 #pragma once
 #include <stdint.h>
 

@@ -243,6 +243,12 @@ void evx_nsga_select(const int32_t* rank, const float* f, int n, int m, int N, i
 // nsga3_select.hip: NSGA-III niche-preserving selection (n ≤ 8192, R ≤ 8192), idx (N,) ascending rows
 void evx_nsga3_niche_select(const int32_t* rank, const int32_t* last_rank, const int64_t* group, const float* group_dist,
                             const int64_t* key, int n, int N, int R, int64_t* idx, hipStream_t s);
+// sra_select.hip: SRA's stochastic ranking (n ≤ evx_sra_rank_max_n(), pc one device word, rank (n,) best first)
+// and its two indicators in one pass (m ≤ evx_sra_indicators_max_m())
+int evx_sra_rank_max_n();
+int evx_sra_indicators_max_m();
+void evx_sra_rank(const float* I1, const float* I2, const float* u, const float* pc, int n, int64_t* rank, hipStream_t s);
+void evx_sra_indicators(const float* obj, int n, int m, float* I1, float* I2, hipStream_t s);
 // sorted-block refinement of a warm-started eigendecomposition (eigh_sbr.hip, evoxmi/ops/sbr.py)
 int evx_sbr_nblocks(int n, int off);
 int evx_sbr_stat_parts();

@@ -2,46 +2,27 @@
 
 Two indicators — I_ε+ fitness (I1) and shift-based density (I2) — are balanced by
 stochastic ranking (a bubble sort choosing the comparison indicator at random with
-probability pc ∈ [0.4, 0.6]).  The bubble sort is sequential by nature; it runs as a
-small host-side C++ op (``evoxmi::stochastic_ranking``).  The reference fills the SDE
-distance matrix only below the diagonal (``sra.py:96-106``), so its I2 ignores later
-individuals; here I2 is the SDE nearest-neighbour distance over all j ≠ i.
+probability pc ∈ [0.4, 0.6]).  The reference fills the SDE distance matrix only below the
+diagonal (``sra.py:96-106``), so its I2 ignores later individuals; here I2 is the SDE
+nearest-neighbour distance over all j ≠ i.
+
+Both steps are ``evoxmi.ops.sra``.  On a HIP device (merged population ≤ 8192 rows, ≤ 16
+objectives) the indicators are one fused pass and the bubble sort runs its sweeps pipelined
+in one workgroup (``sra_select.hip``); pc stays a device word and nothing is read on the
+host, so a whole generation is captured into one hipGraph (``StdWorkflow(..., graph=True)``).
+On the CPU, and above those caps, the indicators are the dense torch expressions and the sort
+is the sequential host op ``evoxmi::stochastic_ranking``; those sizes stay eager-only.
 """
 from __future__ import annotations
-
-import math
 
 import torch
 
 from ...operators import crossover
-from ...ops import _ext
 from ...ops import random as rnd
-from ...utils.common import cal_max
+from ...ops import sra as sra_ops
+from ...ops.sra import _stochastic_rank_host as stochastic_ranking  # noqa: F401  (the host path, under its earlier name)
+from ...ops.sra import sde_distance  # noqa: F401
 from .common import MOAlgorithm
-
-
-def stochastic_ranking(I1, I2, u, pc):
-    if _ext.available():
-        return _ext.ops().stochastic_ranking(I1, I2, u, float(pc)).to(I1.device)
-    n = I1.shape[0]
-    a, b, uu = I1.tolist(), I2.tolist(), u.tolist()
-    r = list(range(n))
-    for _ in range((n + 1) // 2):
-        swapped = False
-        for j in range(n - 1):
-            k = a if uu[j] < pc else b
-            if k[r[j]] < k[r[j + 1]]:
-                r[j], r[j + 1] = r[j + 1], r[j]
-                swapped = True
-        if not swapped:
-            break
-    return torch.tensor(r, device=I1.device)
-
-
-def sde_distance(obj):
-    n = obj.shape[0]
-    d = torch.sqrt((torch.clamp(obj[None, :, :] - obj[:, None, :], min=0) ** 2).sum(-1))  # d[i, j] = ‖max(o_j − o_i, 0)‖
-    return d.masked_fill(torch.eye(n, dtype=torch.bool, device=obj.device), float("inf")).min(1).values
 
 
 class SRA(MOAlgorithm):
@@ -58,10 +39,14 @@ class SRA(MOAlgorithm):
         merged_pop = torch.cat([state.population, state.next_generation], 0)
         merged_fit = torch.cat([state.fitness, fitness], 0)
         key, k_pc, k_env = rnd.split(state.key, 3)
-        pc = float(rnd.uniform(k_pc, ())) * 0.2 + 0.4
-        I = cal_max(merged_fit, merged_fit)
-        I1 = (-torch.exp(-I / 0.05)).sum(0) + 1
-        I2 = sde_distance(merged_fit)
-        u = rnd.uniform(k_env, (merged_fit.shape[0] - 1,))
-        idx = stochastic_ranking(I1, I2, u, pc)[: self.pop_size]
+        n, m = merged_fit.shape
+        if sra_ops.on_device(n, m, merged_fit.device):
+            # the value the host path hands to the op (a double product, cast to float), as a device word
+            pc = (rnd.uniform(k_pc, ()).double() * 0.2 + 0.4).float()
+            I1, I2 = sra_ops.indicators(merged_fit)
+        else:
+            pc = float(rnd.uniform(k_pc, ())) * 0.2 + 0.4
+            I1, I2 = sra_ops.indicators_dense(merged_fit)
+        u = rnd.uniform(k_env, (n - 1,))
+        idx = sra_ops.stochastic_rank(I1, I2, u, pc)[: self.pop_size]
         return state.update(population=merged_pop[idx], fitness=merged_fit[idx], key=key)
