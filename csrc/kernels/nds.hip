@@ -5,8 +5,9 @@
 //    i = 32w + b dominates j (minimisation: ≤ in every objective, < in at least one).
 //    Word-major so a wave's 64 lanes (64 consecutive j) read 256 contiguous bytes.
 //    The 32 candidates of word w are staged in LDS.
-// 2. peel kernel: a chip-wide persistent grid (≤ 256 workgroups of 64 rows × 4 word
-//    quarters, all co-resident on the 256 CUs) computes one front per iteration.  j joins front k iff every
+// 2. peel kernel: a chip-wide persistent grid (workgroups of 64 rows × PEEL_PARTS word
+//    parts, at most PEEL_MAX_PER_CU per CU so that all are co-resident; more rows than the
+//    grid covers take further row passes) computes one front per iteration.  j joins front k iff every
 //    dominator of j is already ranked:  DW[w][j] & ~R[w] == 0 for all w, where R is
 //    the ranked bitset (early exit at the first word with an unranked dominator; the
 //    next front's test of the same row resumes at that word).  R is double-buffered and only ever OR-ed
@@ -55,8 +56,9 @@ __global__ void __launch_bounds__(256) dominance_kernel(const float* __restrict_
 }
 
 // workspace layout (uint32): [0] barrier count, [1] barrier generation, [2] error flag,
-// [3] ranked total, [4 .. 4+nw) R0, [4+nw .. 4+2nw) R1, [4+2nw .. 4+2nw+n+1) left[k],
-// then 4n words: per-(row, word-quarter) resume word (words before it hold only ranked
+// [3] unused, [4 .. 4+nw) R0, [4+nw .. 4+2nw) R1, [4+2nw .. 4+2nw+n+1) left[k] (rows still
+// unranked after front k: written only during iteration k, so stable once barrier k is passed),
+// then PEEL_PARTS·n words: per-(row, word-part) resume word (words before it hold only ranked
 // dominators, and R only grows, so each scan continues where the previous front's stopped)
 constexpr int kSpinLimit = 1 << 24;
 
@@ -102,7 +104,7 @@ __global__ void __launch_bounds__(64 * PEEL_PARTS) peel_kernel(const uint32_t* _
                                                    int barrier_extra) {
   uint32_t* R[2] = {ws + 4, ws + 4 + nw};
   uint32_t* left = ws + 4 + 2 * nw;
-  uint32_t* wptr = left + n + 1;  // 4 per row
+  uint32_t* wptr = left + n + 1;  // PEEL_PARTS per row
   const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
   const int qlen = (nw + PEEL_PARTS - 1) / PEEL_PARTS, w0q = q * qlen, w1q = min(nw, w0q + qlen);
   __shared__ uint32_t Rs[PEEL_MAXW];
@@ -126,7 +128,7 @@ __global__ void __launch_bounds__(64 * PEEL_PARTS) peel_kernel(const uint32_t* _
       if (v) __hip_atomic_fetch_or(&Rn[w], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();
-    uint32_t my_left = 0, my_ranked = 0;  // my_ranked: lane-uniform in wave 0
+    uint32_t my_left = 0;
     for (int jb = blockIdx.x * 64, pass = 0; jb < n; jb += rows_per_pass, ++pass) {
       const int j = jb + lane;
       const bool active = j < n && !done_s[pass][lane];
@@ -150,7 +152,7 @@ __global__ void __launch_bounds__(64 * PEEL_PARTS) peel_kernel(const uint32_t* _
       __syncthreads();
       if (q == 0) {
         // wave 0 owns the 64 rows: ballot the new front members, one atomic OR per 32-row
-        // word (jb is a multiple of 64) and one ranked-count add per workgroup per front
+        // word (jb is a multiple of 64) and one unranked-count add per workgroup per front
         bool any_fail = false;
 #pragma unroll
         for (int p2 = 0; p2 < PEEL_PARTS; ++p2) any_fail |= fail_q[p2][lane];
@@ -164,7 +166,6 @@ __global__ void __launch_bounds__(64 * PEEL_PARTS) peel_kernel(const uint32_t* _
         }
         if (lane == 0 && (uint32_t)m) __hip_atomic_fetch_or(&Rn[jb >> 5], (uint32_t)m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (lane == 32 && (uint32_t)(m >> 32)) __hip_atomic_fetch_or(&Rn[(jb >> 5) + 1], (uint32_t)(m >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        my_ranked += __popcll(m);
       }
       __syncthreads();
     }
@@ -172,8 +173,6 @@ __global__ void __launch_bounds__(64 * PEEL_PARTS) peel_kernel(const uint32_t* _
     __syncthreads();
     if (threadIdx.x == 0 && wg_left)
       __hip_atomic_fetch_add(&left[k], wg_left, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (threadIdx.x == 0 && my_ranked)
-      __hip_atomic_fetch_add(&ws[3], my_ranked, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (!grid_barrier(ws, gridDim.x + barrier_extra, gen)) {
       // a workgroup never arrived (not co-resident): rows not ranked yet go last (rank n,
       // never the best front) and the sticky device error word tells the host
@@ -183,9 +182,11 @@ __global__ void __launch_bounds__(64 * PEEL_PARTS) peel_kernel(const uint32_t* _
       return;
     }
     const uint32_t still = __hip_atomic_load(&left[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t done = __hip_atomic_load(&ws[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (still == 0) return;
-    if ((int)done >= limit || k + 1 >= n) {
+    // the ranked total comes from left[k], which no workgroup touches after barrier k, so every
+    // thread of the grid takes the same decision (a running total that iteration k+1 already
+    // adds to could split the grid around `limit` and strand the rest at the next barrier)
+    if (n - (int)still >= limit || k + 1 >= n) {
       for (int jb = blockIdx.x * 64, pass = 0; jb < n; jb += rows_per_pass, ++pass)
         if (q == 0 && jb + lane < n && !done_s[pass][lane]) rank[jb + lane] = n;
       return;
@@ -203,8 +204,16 @@ size_t evx_nds_workspace_words(int n) { return 4 + 2 * (size_t)((n + 31) / 32) +
 
 // Workgroups the persistent peel may use: every one must be co-resident for the grid
 // barrier, so the grid is capped by the device's CU count × the kernel's occupancy
-// (hipOccupancy… on this kernel), not by a hard-coded 256.  Returns 0 if the peel cannot
-// run co-resident at this n (the caller falls back to the host-orchestrated peel).
+// (hipOccupancy… on this kernel), not by a hard-coded 256.  The occupancy query is advisory:
+// it answers 4 workgroups per CU for this kernel (40 VGPRs, 8 waves per SIMD), but with
+// 81–96 SGPRs allocated the hardware admits 7 waves per SIMD, i.e. 3 of these 512-thread
+// workgroups, and the 4th queues until a resident one exits, which a grid barrier never
+// lets happen (n = 65536 timed out at the first barrier).  PEEL_MAX_PER_CU keeps a margin
+// below that edge (4 waves per SIMD); larger n take more row passes per workgroup instead.
+// Returns 0 if the peel cannot run co-resident at this n (the caller falls back to the
+// host-orchestrated peel).
+constexpr int PEEL_MAX_PER_CU = 2;
+
 int evx_nds_peel_blocks(int n) {
   static int capacity = -1;
   if (capacity < 0) {
@@ -212,7 +221,7 @@ int evx_nds_peel_blocks(int n) {
     hipGetDevice(&dev);
     hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, peel_kernel, 64 * PEEL_PARTS, 0) != hipSuccess) per_cu = 0;
-    capacity = cus * per_cu;
+    capacity = cus * min(per_cu, PEEL_MAX_PER_CU);
   }
   static const int cap = [] { const char* e = getenv("EVOXMI_NDS_BLOCKS"); const int v = e ? atoi(e) : (1 << 30); return v < 1 ? 1 : v; }();
   int blocks = min(min((n + 63) / 64, cap), capacity);

@@ -1,10 +1,17 @@
 // NSGA-II environmental selection after the non-dominated sort (K10 of SURVEY §2.10;
 // reference algorithms/mo/nsga2.py:86-100 and operators/selection/non_dominate.py:116-204).
 //
-// Semantics reproduced exactly: worst = sorted(rank)[mask_pos]; crowding distance on the
-// front `rank == worst` (per objective: stable sort by cost, extremes +inf, interior
+// Semantics: worst = sorted(rank)[mask_pos]; crowding distance on the front
+// `rank == worst` (per objective: stable sort by cost, extremes +inf, interior
 // (c[p+1] − c[p−1]) / (c[last] − c[0]), summed over objectives; rows outside the front
 // get −inf); survivors = lexsort((−cd, rank))[:N] (stable: ties by row index).
+//
+// The survivors are identical to the torch path (ops/nds.py:crowding_distance + lexsort)
+// for finite objectives.  The crowding distance here is computed on the cut front alone:
+// only its rows are sorted.  The torch path sorts all n rows with the masked-out ones keyed
+// +inf, so a cut-front row that holds +inf (or NaN) ties with (or sorts after) masked rows
+// there, its "last valid" slot can be a masked row, and the survivors then differ from this
+// kernel's whenever other rows are masked out.
 //
 // One workgroup of 1024 threads × 8 items does it all on chip (n ≤ 8192).  Every sort is
 // rocPRIM's stable LDS block radix sort with the items held in registers (blocked

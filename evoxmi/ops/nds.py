@@ -50,7 +50,12 @@ def crowding_distance(costs: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
 def nsga2_survivors(f: torch.Tensor, N: int, mask_pos: int, until: int = 0) -> torch.Tensor:
     """Indices of the N survivors of NSGA-II environmental selection (rank, then crowding
     distance on the front ``rank == sorted(rank)[mask_pos]``, lexsort order) — the fused
-    ``nsga_select.hip`` kernel after the device non-dominated sort (n ≤ 8192)."""
+    ``nsga_select.hip`` kernel after the device non-dominated sort (n ≤ 8192).
+
+    Identical to the torch path (``crowding_distance`` + lexsort) for finite objectives.  The
+    kernel computes the crowding distance on the cut front alone; the torch path sorts all
+    rows with the masked-out ones keyed ``+inf``, so the two differ when a cut-front row
+    holds ``+inf`` (or NaN) while other rows are masked out."""
     f = f.to(torch.float32).contiguous()
     rank = non_dominated_sort(f, until)
     return _ext.ops().nsga_select(rank, f, int(N), int(mask_pos))
