@@ -244,10 +244,6 @@ at::Tensor gemm_h3_rowterms(const at::Tensor& A, const at::Tensor& a_rinv, int64
   return out;
 }
 
-int64_t h3_elems(int64_t rows, int64_t K) { return evx_h3_elems(rows, (int)K); }
-
-int64_t blk_elems(int64_t rows, int64_t K) { return evx_blk_elems(rows, (int)K); }
-int64_t blk_rows(int64_t rows) { return evx_blk_rows(rows); }
 int64_t gemm_blk_tile(int64_t which) { return which == 0 ? evx_gemm_blk_tile_m() : evx_gemm_blk_tile_n(); }
 
 }  // namespace
@@ -257,14 +253,11 @@ TORCH_LIBRARY_FRAGMENT(evoxmi, m) {
   m.def("blk_philox_normal(Tensor key, int rows, int d, int row0=0, Tensor(a!)? out=None) -> Tensor");
   m.def("gemm_blk(Tensor A, int M, Tensor B, int N, int K, float alpha=1., Tensor? alpha_ptr=None, Tensor? bias_n=None, "
         "Tensor(a!)? out=None, Tensor? skip=None) -> Tensor");
-  m.def("blk_elems(int rows, int K) -> int");
   m.def("h3_split(Tensor X, Tensor? sub_k=None, Tensor? colscale=None, Tensor(a!)? out=None, Tensor(b!)? rinv_out=None) -> Tensor[]");
   m.def("h3_philox_normal(Tensor key, int rows, int d, int row0=0, Tensor(a!)? out=None, Tensor(b!)? rinv_out=None) -> Tensor[]");
   m.def("gemm_h3(Tensor A, Tensor a_rinv, int M, Tensor B, Tensor b_rinv, int N, int K, float alpha=1., Tensor? alpha_ptr=None, "
         "Tensor? bias_n=None, Tensor(a!)? out=None, Tensor? skip=None, int sub_cols=0) -> Tensor");
   m.def("gemm_h3_rowterms(Tensor A, Tensor a_rinv, int M, Tensor B, Tensor b_rinv, int N, int K, float alpha, int fid) -> Tensor");
-  m.def("h3_elems(int rows, int K) -> int");
-  m.def("blk_rows(int rows) -> int");
   m.def("gemm_blk_tile(int which) -> int");
 }
 
@@ -279,8 +272,5 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
 }
 
 TORCH_LIBRARY_IMPL(evoxmi, CompositeExplicitAutograd, m) {
-  m.impl("blk_elems", &blk_elems);
-  m.impl("h3_elems", &h3_elems);
-  m.impl("blk_rows", &blk_rows);
   m.impl("gemm_blk_tile", &gemm_blk_tile);
 }

@@ -162,43 +162,46 @@ at::Tensor gemm_f32(const at::Tensor& A, int64_t a_rc, const c10::optional<at::T
   return C;
 }
 
+// float4 access: 16-byte aligned base and a row stride divisible by 4
+bool vec4_ok(const at::Tensor& t) { return (reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0) && (t.stride(0) % 4 == 0); }
+
 // K-split register-direct f32 GEMM (gemm_ks.hip).  A: a_kc → (M, K) rows, else (K, M);
 // B: b_kc → (N, K) rows (C = A·Bᵀ), else (K, N) (C = A·B).  Inner strides must be 1.
-at::Tensor gemm_ks(const at::Tensor& A, int64_t a_kc, const at::Tensor& B, int64_t b_kc, int64_t M, int64_t N, int64_t K,
-                   int64_t mode, double alpha, const c10::optional<at::Tensor>& alpha_ptr,
-                   const c10::optional<at::Tensor>& bias_n, double beta, const c10::optional<at::Tensor>& Cin,
-                   const c10::optional<at::Tensor>& out, const c10::optional<at::Tensor>& skip,
-                   const c10::optional<at::Tensor>& a_sub_k, const c10::optional<at::Tensor>& sel = c10::nullopt,
-                   const c10::optional<at::Tensor>& A2 = c10::nullopt, double alpha2 = 0.0,
-                   const c10::optional<at::Tensor>& C2 = c10::nullopt, const c10::optional<at::Tensor>& stat_part = c10::nullopt,
-                   int64_t stat_diag_only = 0, int64_t prec = 0, double diag_add = 0.0) {
+// The one place that checks the arguments of a gemm_ks launch and fills its struct: `op` names
+// the calling op in error messages, `a` carries what that op has already decided (the stacked
+// product's sub_cols / sub_ld / force_tile).
+at::Tensor gemm_ks_run(const char* op, EvxGemmKs a, const at::Tensor& A, int64_t a_kc, const at::Tensor& B, int64_t b_kc, int64_t M,
+                       int64_t N, int64_t K, int64_t mode, double alpha, const c10::optional<at::Tensor>& alpha_ptr,
+                       const c10::optional<at::Tensor>& bias_n, double beta, const c10::optional<at::Tensor>& Cin,
+                       const c10::optional<at::Tensor>& out, const c10::optional<at::Tensor>& skip,
+                       const c10::optional<at::Tensor>& a_sub_k, const c10::optional<at::Tensor>& sel = c10::nullopt,
+                       const c10::optional<at::Tensor>& A2 = c10::nullopt, double alpha2 = 0.0,
+                       const c10::optional<at::Tensor>& C2 = c10::nullopt,
+                       const c10::optional<at::Tensor>& stat_part = c10::nullopt, int64_t stat_diag_only = 0, int64_t prec = 0,
+                       double diag_add = 0.0) {
   CHECK_DEV(A); CHECK_F32(A); CHECK_DEV(B); CHECK_F32(B);
-  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.stride(1) == 1 && B.stride(1) == 1, "gemm_ks: 2-D operands with unit inner stride");
-  TORCH_CHECK(M > 0 && N > 0 && K > 0, "gemm_ks: empty shape");
-  TORCH_CHECK(mode >= 0 && mode <= 2, "gemm_ks: mode");
-  if (a_kc) { TORCH_CHECK(A.size(0) >= M && A.size(1) >= K, "gemm_ks: A shape"); } else { TORCH_CHECK(A.size(0) >= K && A.size(1) >= M, "gemm_ks: A shape"); }
-  if (b_kc) { TORCH_CHECK(B.size(0) >= N && B.size(1) >= K, "gemm_ks: B shape"); } else { TORCH_CHECK(B.size(0) >= K && B.size(1) >= N, "gemm_ks: B shape"); }
-  auto vec4_ok = [](const at::Tensor& t) {
-    return (reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0) && (t.stride(0) % 4 == 0);
-  };
-  if (a_kc || b_kc) { TORCH_CHECK(K % 4 == 0, "gemm_ks: K-contiguous operands need K % 4 == 0"); }
-  if (a_kc) { TORCH_CHECK(vec4_ok(A), "gemm_ks: A must be 16-byte aligned with a row stride divisible by 4"); }
-  if (b_kc) { TORCH_CHECK(vec4_ok(B), "gemm_ks: B must be 16-byte aligned with a row stride divisible by 4"); }
+  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.stride(1) == 1 && B.stride(1) == 1, op, ": 2-D operands with unit inner stride");
+  TORCH_CHECK(M > 0 && N > 0 && K > 0, op, ": empty shape");
+  TORCH_CHECK(mode >= 0 && mode <= 2, op, ": mode");
+  if (a_kc) { TORCH_CHECK(A.size(0) >= M && A.size(1) >= K, op, ": A shape"); } else { TORCH_CHECK(A.size(0) >= K && A.size(1) >= M, op, ": A shape"); }
+  if (b_kc) { TORCH_CHECK(B.size(0) >= N && B.size(1) >= K, op, ": B shape"); } else { TORCH_CHECK(B.size(0) >= K && B.size(1) >= N, op, ": B shape"); }
+  if (a_kc || b_kc) { TORCH_CHECK(K % 4 == 0, op, ": K-contiguous operands need K % 4 == 0"); }
+  if (a_kc) { TORCH_CHECK(vec4_ok(A), op, ": A must be 16-byte aligned with a row stride divisible by 4"); }
+  if (b_kc) { TORCH_CHECK(vec4_ok(B), op, ": B must be 16-byte aligned with a row stride divisible by 4"); }
   if (mode != 0) {
-    TORCH_CHECK(M == N, "gemm_ks: symmetric / skew outputs need M == N");
+    TORCH_CHECK(M == N, op, ": symmetric / skew outputs need M == N");
     TORCH_CHECK(!(bias_n.has_value() && bias_n->defined()) && !(Cin.has_value() && Cin->defined()),
-                "gemm_ks: symmetric / skew outputs take no bias / Cin");
+                op, ": symmetric / skew outputs take no bias / Cin");
   }
   c10::DeviceGuard g(A.device());
   at::Tensor C;
   if (out.has_value() && out->defined()) {
     C = *out;
     CHECK_DEV(C); CHECK_F32(C);
-    TORCH_CHECK(C.dim() == 2 && C.stride(1) == 1 && C.size(0) >= M && C.size(1) >= N, "gemm_ks: out shape");
+    TORCH_CHECK(C.dim() == 2 && C.stride(1) == 1 && C.size(0) >= M && C.size(1) >= N, op, ": out shape");
   } else {
     C = at::empty({M, N}, A.options());
   }
-  EvxGemmKs a{};
   a.A = A.data_ptr<float>();
   a.lda = A.stride(0);
   a.B = B.data_ptr<float>();
@@ -211,53 +214,53 @@ at::Tensor gemm_ks(const at::Tensor& A, int64_t a_kc, const at::Tensor& B, int64
   a.alpha_ptr = optf(alpha_ptr);
   if (bias_n.has_value() && bias_n->defined()) {
     CHECK_DEV(*bias_n); CHECK_F32(*bias_n); CHECK_CONTIG(*bias_n);
-    TORCH_CHECK(bias_n->numel() >= N, "gemm_ks: bias length");
+    TORCH_CHECK(bias_n->numel() >= N, op, ": bias length");
     a.bias_n = bias_n->data_ptr<float>();
   }
   a.beta = (float)beta;
   if (Cin.has_value() && Cin->defined()) {
     CHECK_DEV(*Cin); CHECK_F32(*Cin);
-    TORCH_CHECK(Cin->dim() == 2 && Cin->stride(1) == 1 && Cin->size(0) >= M && Cin->size(1) >= N, "gemm_ks: Cin shape");
+    TORCH_CHECK(Cin->dim() == 2 && Cin->stride(1) == 1 && Cin->size(0) >= M && Cin->size(1) >= N, op, ": Cin shape");
     a.Cin = Cin->data_ptr<float>();
     a.ldcin = Cin->stride(0);
   }
   if (skip.has_value() && skip->defined()) {
     CHECK_DEV(*skip);
-    TORCH_CHECK(skip->scalar_type() == at::kInt && skip->numel() >= 1, "gemm_ks: skip must be int32");
+    TORCH_CHECK(skip->scalar_type() == at::kInt && skip->numel() >= 1, op, ": skip must be int32");
     a.skip = skip->data_ptr<int32_t>();
   }
   if (a_sub_k.has_value() && a_sub_k->defined()) {
     CHECK_DEV(*a_sub_k); CHECK_F32(*a_sub_k); CHECK_CONTIG(*a_sub_k);
     TORCH_CHECK(a_kc && a_sub_k->numel() >= K && reinterpret_cast<uintptr_t>(a_sub_k->data_ptr()) % 16 == 0,
-                "gemm_ks: a_sub_k needs a K-contiguous A and a 16-byte aligned vector of length ≥ K");
+                op, ": a_sub_k needs a K-contiguous A and a 16-byte aligned vector of length ≥ K");
     a.a_sub_k = a_sub_k->data_ptr<float>();
   }
   if (sel.has_value() && sel->defined()) {
     CHECK_DEV(*sel);
-    TORCH_CHECK(sel->scalar_type() == at::kInt && sel->numel() >= 1, "gemm_ks: sel must be int32");
+    TORCH_CHECK(sel->scalar_type() == at::kInt && sel->numel() >= 1, op, ": sel must be int32");
     a.sel = sel->data_ptr<int32_t>();
     a.alpha2 = (float)alpha2;
     if (A2.has_value() && A2->defined()) {
-      TORCH_CHECK(A2->sizes() == A.sizes() && A2->strides() == A.strides() && A2->scalar_type() == at::kFloat, "gemm_ks: A2 like A");
-      TORCH_CHECK(!a_kc || vec4_ok(*A2), "gemm_ks: A2 alignment");
+      TORCH_CHECK(A2->sizes() == A.sizes() && A2->strides() == A.strides() && A2->scalar_type() == at::kFloat, op, ": A2 like A");
+      TORCH_CHECK(!a_kc || vec4_ok(*A2), op, ": A2 alignment");
       a.A2 = A2->data_ptr<float>();
     }
     if (C2.has_value() && C2->defined()) {
-      TORCH_CHECK(C2->sizes() == C.sizes() && C2->strides() == C.strides() && C2->scalar_type() == at::kFloat, "gemm_ks: C2 like out");
-      TORCH_CHECK(vec4_ok(*C2) == vec4_ok(C), "gemm_ks: C2 alignment");
+      TORCH_CHECK(C2->sizes() == C.sizes() && C2->strides() == C.strides() && C2->scalar_type() == at::kFloat, op, ": C2 like out");
+      TORCH_CHECK(vec4_ok(*C2) == vec4_ok(C), op, ": C2 alignment");
       a.C2 = C2->data_ptr<float>();
     }
   }
   if (stat_part.has_value() && stat_part->defined()) {
-    TORCH_CHECK(mode == 1, "gemm_ks: stats partials need the symmetric mode");
+    TORCH_CHECK(mode == 1, op, ": stats partials need the symmetric mode");
     CHECK_DEV(*stat_part);
     TORCH_CHECK(stat_part->scalar_type() == at::kDouble && stat_part->is_contiguous() &&
-                stat_part->numel() >= 4 * (int64_t)evx_gemm_ks_grid((int)M, (int)N, (int)mode), "gemm_ks: stat_part float64[4·grid]");
+                stat_part->numel() >= 4 * (int64_t)evx_gemm_ks_grid((int)M, (int)N, (int)mode), op, ": stat_part float64[4·grid]");
     a.stat_part = stat_part->data_ptr<double>();
     a.stat_diag_only = (int)stat_diag_only;
   }
-  TORCH_CHECK(prec == 0 || prec == 3, "gemm_ks: prec 0 (process default) or 3 (bf16x3)");
-  TORCH_CHECK(diag_add == 0.0 || M == N, "gemm_ks: diag_add needs a square output");
+  TORCH_CHECK(prec == 0 || prec == 3, op, ": prec 0 (process default) or 3 (bf16x3)");
+  TORCH_CHECK(diag_add == 0.0 || M == N, op, ": diag_add needs a square output");
   a.prec = (int)prec;
   a.diag_add = (float)diag_add;
   a.c_vec4 = vec4_ok(C) ? 1 : 0;
@@ -265,84 +268,24 @@ at::Tensor gemm_ks(const at::Tensor& A, int64_t a_kc, const at::Tensor& B, int64
   return C;
 }
 
-// C = alpha·(*alpha_ptr)·op(A)·op(B)ᵀ (+ bias_n) for K-contiguous operands, either of which may be
-// given as bf16x6 fragment planes (int16 [3][rows][kp], split_planes / philox_normal_planes)
-at::Tensor gemm_ks_pl(const c10::optional<at::Tensor>& A, const c10::optional<at::Tensor>& a_pl, const c10::optional<at::Tensor>& B,
-                      const c10::optional<at::Tensor>& b_pl, int64_t M, int64_t N, int64_t K, double alpha,
-                      const c10::optional<at::Tensor>& alpha_ptr, const c10::optional<at::Tensor>& bias_n,
-                      const c10::optional<at::Tensor>& out, const c10::optional<at::Tensor>& a_sub_k, int64_t sub_cols, int64_t sub_ld) {
-  const bool ha = A.has_value() && A->defined(), hap = a_pl.has_value() && a_pl->defined();
-  const bool hb = B.has_value() && B->defined(), hbp = b_pl.has_value() && b_pl->defined();
-  TORCH_CHECK(ha && hb && !hap && !hbp, "gemm_ks_pl: f32 operands (fragment planes were removed in round 6)");
-  TORCH_CHECK(M > 0 && N > 0 && K > 0 && K % 4 == 0, "gemm_ks_pl: shape (K % 4 == 0)");
-  const int64_t kp = (K + 31) / 32 * 32;
-  auto vec4_ok = [](const at::Tensor& t) { return (reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0) && (t.stride(0) % 4 == 0); };
-  auto check_pl = [&](const at::Tensor& t, int64_t rows, const char* w) {
-    CHECK_DEV(t);
-    TORCH_CHECK(t.scalar_type() == at::kShort && t.dim() == 3 && t.size(0) == 3 && t.size(1) >= rows && t.size(2) == kp && t.is_contiguous(),
-                "gemm_ks_pl: ", w, " planes int16 [3, rows, kp]");
-  };
+// Stacked products that share A (the CEC'22 composition rotations) in one launch, K-contiguous
+// operands: C = alpha·(*alpha_ptr)·(A − shift_c)·Bᵀ (+ bias_n), where output columns
+// [c·sub_cols, (c+1)·sub_cols) use the shift row a_sub_k + c·sub_ld (sub_cols 0: one shift)
+at::Tensor gemm_ks_stacked(const at::Tensor& A, const at::Tensor& B, int64_t M, int64_t N, int64_t K, double alpha,
+                           const c10::optional<at::Tensor>& alpha_ptr, const c10::optional<at::Tensor>& bias_n,
+                           const c10::optional<at::Tensor>& out, const at::Tensor& a_sub_k, int64_t sub_cols, int64_t sub_ld) {
+  TORCH_CHECK(M > 0 && N > 0 && K > 0 && K % 4 == 0, "gemm_ks_stacked: shape (K % 4 == 0)");
   EvxGemmKs a{};
-  const at::Tensor& ref = ha ? *A : *a_pl;
-  if (ha) {
-    CHECK_DEV(*A); CHECK_F32(*A);
-    TORCH_CHECK(A->dim() == 2 && A->stride(1) == 1 && A->size(0) >= M && A->size(1) >= K && vec4_ok(*A), "gemm_ks_pl: A");
-    a.A = A->data_ptr<float>();
-    a.lda = A->stride(0);
-  } else {
-    check_pl(*a_pl, M, "A");
-    a.a_pl = reinterpret_cast<const uint16_t*>(a_pl->data_ptr<int16_t>());
-    a.a_pl_rows = a_pl->size(1);
+  if (sub_cols > 0) {
+    int t = evx_gemm_ks_tile((int)M, (int)N, 0);
+    if (sub_cols % (t == 8 ? 64 : 16 * t)) t = a.force_tile = (M >= 2048 ? 8 : 4);  // 64-wide tiles
+    const int bn = t == 8 ? 64 : 16 * t;
+    TORCH_CHECK(sub_cols % bn == 0 && sub_ld % 4 == 0 && sub_ld >= K && a_sub_k.numel() >= ((N + sub_cols - 1) / sub_cols - 1) * sub_ld + K,
+                "gemm_ks_stacked: per-block shifts need sub_cols a multiple of the tile width (", bn, ") and one shift row per block");
+    a.sub_cols = (int)sub_cols;
+    a.sub_ld = sub_ld;
   }
-  if (hb) {
-    CHECK_DEV(*B); CHECK_F32(*B);
-    TORCH_CHECK(B->dim() == 2 && B->stride(1) == 1 && B->size(0) >= N && B->size(1) >= K && vec4_ok(*B), "gemm_ks_pl: B");
-    a.B = B->data_ptr<float>();
-    a.ldb = B->stride(0);
-  } else {
-    check_pl(*b_pl, N, "B");
-    a.b_pl = reinterpret_cast<const uint16_t*>(b_pl->data_ptr<int16_t>());
-    a.b_pl_rows = b_pl->size(1);
-  }
-  a.pl_kp = kp;
-  c10::DeviceGuard g(ref.device());
-  at::Tensor C;
-  if (out.has_value() && out->defined()) {
-    C = *out;
-    CHECK_DEV(C); CHECK_F32(C);
-    TORCH_CHECK(C.dim() == 2 && C.stride(1) == 1 && C.size(0) >= M && C.size(1) >= N, "gemm_ks_pl: out shape");
-  } else {
-    C = at::empty({M, N}, ref.options().dtype(at::kFloat));
-  }
-  a.C = C.data_ptr<float>();
-  a.ldc = C.stride(0);
-  a.M = (int)M; a.N = (int)N; a.K = (int)K;
-  a.a_kc = 1; a.b_kc = 1; a.mode = 0;
-  a.alpha = (float)alpha;
-  a.alpha_ptr = optf(alpha_ptr);
-  if (bias_n.has_value() && bias_n->defined()) {
-    CHECK_DEV(*bias_n); CHECK_F32(*bias_n); CHECK_CONTIG(*bias_n);
-    TORCH_CHECK(bias_n->numel() >= N, "gemm_ks_pl: bias length");
-    a.bias_n = bias_n->data_ptr<float>();
-  }
-  if (a_sub_k.has_value() && a_sub_k->defined()) {
-    CHECK_DEV(*a_sub_k); CHECK_F32(*a_sub_k); CHECK_CONTIG(*a_sub_k);
-    TORCH_CHECK(ha && a_sub_k->numel() >= K && reinterpret_cast<uintptr_t>(a_sub_k->data_ptr()) % 16 == 0,
-                "gemm_ks_pl: a_sub_k needs an f32 A (16-byte aligned, length ≥ K)");
-    a.a_sub_k = a_sub_k->data_ptr<float>();
-    if (sub_cols > 0) {
-      int t = evx_gemm_ks_tile((int)M, (int)N, 0);
-      if (sub_cols % (t == 8 ? 64 : 16 * t)) t = a.force_tile = (M >= 2048 ? 8 : 4);  // 64-wide tiles
-      const int bn = t == 8 ? 64 : 16 * t;
-      TORCH_CHECK(sub_cols % bn == 0 && sub_ld % 4 == 0 && sub_ld >= K && a_sub_k->numel() >= ((N + sub_cols - 1) / sub_cols - 1) * sub_ld + K,
-                  "gemm_ks_pl: per-block shifts need sub_cols a multiple of the tile width (", bn, ") and one shift row per block");
-      a.sub_cols = (int)sub_cols;
-      a.sub_ld = sub_ld;
-    }
-  }
-  a.c_vec4 = vec4_ok(C) ? 1 : 0;
-  evx_gemm_ks(a, cur_stream());
-  return C;
+  return gemm_ks_run("gemm_ks_stacked", a, A, 1, B, 1, M, N, K, 0, alpha, alpha_ptr, bias_n, 0.0, c10::nullopt, out, c10::nullopt, a_sub_k);
 }
 
 void gemm_ks_set_tile(int64_t t) { evx_gemm_ks_set_tile((int)t); }
@@ -353,7 +296,7 @@ at::Tensor gemm_ks_new(const at::Tensor& A, int64_t a_kc, const at::Tensor& B, i
                        int64_t mode, double alpha, const c10::optional<at::Tensor>& alpha_ptr,
                        const c10::optional<at::Tensor>& bias_n, double beta, const c10::optional<at::Tensor>& Cin,
                        const c10::optional<at::Tensor>& skip, const c10::optional<at::Tensor>& a_sub_k) {
-  return gemm_ks(A, a_kc, B, b_kc, M, N, K, mode, alpha, alpha_ptr, bias_n, beta, Cin, c10::nullopt, skip, a_sub_k);
+  return gemm_ks_run("gemm_ks", {}, A, a_kc, B, b_kc, M, N, K, mode, alpha, alpha_ptr, bias_n, beta, Cin, c10::nullopt, skip, a_sub_k);
 }
 
 void gemm_ks_out(const at::Tensor& A, int64_t a_kc, const at::Tensor& B, int64_t b_kc, int64_t M, int64_t N, int64_t K,
@@ -362,8 +305,8 @@ void gemm_ks_out(const at::Tensor& A, int64_t a_kc, const at::Tensor& B, int64_t
                  const c10::optional<at::Tensor>& a_sub_k, const c10::optional<at::Tensor>& sel, const c10::optional<at::Tensor>& A2,
                  double alpha2, const c10::optional<at::Tensor>& C2, const c10::optional<at::Tensor>& stat_part, int64_t stat_diag_only,
                  int64_t prec, double diag_add) {
-  gemm_ks(A, a_kc, B, b_kc, M, N, K, mode, alpha, alpha_ptr, bias_n, beta, Cin, out, skip, a_sub_k, sel, A2, alpha2, C2, stat_part,
-          stat_diag_only, prec, diag_add);
+  gemm_ks_run("gemm_ks_out", {}, A, a_kc, B, b_kc, M, N, K, mode, alpha, alpha_ptr, bias_n, beta, Cin, out, skip, a_sub_k, sel, A2, alpha2,
+              C2, stat_part, stat_diag_only, prec, diag_add);
 }
 
 int64_t gemm_ks_grid(int64_t M, int64_t N, int64_t mode) { return evx_gemm_ks_grid((int)M, (int)N, (int)mode); }
@@ -378,8 +321,7 @@ at::Tensor cec_rotated_rowterms(const at::Tensor& X, const at::Tensor& Mrot, con
   TORCH_CHECK(X.dim() == 2 && Mrot.dim() == 2 && X.stride(1) == 1 && Mrot.stride(1) == 1, "cec_rotated_rowterms: 2-D row-major operands");
   const int64_t N = X.size(0), D = X.size(1);
   TORCH_CHECK(Mrot.size(0) == D && Mrot.size(1) == D && o.numel() >= D, "cec_rotated_rowterms: shapes");
-  TORCH_CHECK(D % 4 == 0 && X.stride(0) % 4 == 0 && Mrot.stride(0) % 4 == 0 && reinterpret_cast<uintptr_t>(X.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(Mrot.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(o.data_ptr()) % 16 == 0,
+  TORCH_CHECK(D % 4 == 0 && vec4_ok(X) && vec4_ok(Mrot) && reinterpret_cast<uintptr_t>(o.data_ptr()) % 16 == 0,
               "cec_rotated_rowterms: 16-byte aligned operands, D % 4 == 0");
   const int t = evx_gemm_ks_tile((int)N, (int)D, 0);
   TORCH_CHECK(t == 8 || t == 4, "cec_rotated_rowterms: the row-terms epilogue needs a 64-column tile layout");
@@ -419,16 +361,6 @@ void sbr16_block_out(const at::Tensor& A, int64_t shift, int64_t sweeps, int64_t
                   dq.data_ptr<float>(), (int)sb, cur_stream(), skip.data_ptr<int>(), (float)skip_tol);
 }
 
-void sbr16_far_out(const at::Tensor& A, const at::Tensor& perm, const at::Tensor& Q, const at::Tensor& dq, const at::Tensor& stats,
-                   double thr_fac, const at::Tensor& theta, at::Tensor& X, int64_t sb, const at::Tensor& skip) {
-  const int64_t n = A.size(0);
-  TORCH_CHECK(X.sizes() == A.sizes() && X.stride(1) == 1 && stats.scalar_type() == at::kDouble && theta.scalar_type() == at::kFloat,
-              "sbr16_far_out: shapes");
-  evx_sbr16_far(A.data_ptr<float>(), (int)n, A.stride(0), perm.data_ptr<int>(), Q.data_ptr<float>(), dq.data_ptr<float>(),
-                stats.data_ptr<double>(), (float)thr_fac, 0.f, X.data_ptr<float>(), X.stride(0), (int)sb, cur_stream(),
-                theta.data_ptr<float>(), skip.data_ptr<int>());
-}
-
 void sbr16_far_bq_out(const at::Tensor& A, const at::Tensor& perm, const at::Tensor& Q, const at::Tensor& dq, const at::Tensor& stats,
                       double thr_fac, const at::Tensor& theta, at::Tensor& X, const at::Tensor& B, at::Tensor& Bq, int64_t sb,
                       const at::Tensor& skip_far, const at::Tensor& skip_bq, bool pre) {
@@ -443,13 +375,6 @@ void sbr16_far_bq_out(const at::Tensor& A, const at::Tensor& perm, const at::Ten
                    stats.data_ptr<double>(), (float)thr_fac, theta.data_ptr<float>(), X.data_ptr<float>(), X.stride(0), B.data_ptr<float>(),
                    (int)B.size(0), B.stride(0), Bq.data_ptr<float>(), Bq.stride(0), (int)sb, cur_stream(), skip_far.data_ptr<int>(),
                    skip_bq.data_ptr<int>(), pre);
-}
-
-void sbr16_bq_out(const at::Tensor& B, const at::Tensor& perm, const at::Tensor& Q, at::Tensor& Bq, int64_t sb, const at::Tensor& skip) {
-  const int64_t n = B.size(1);
-  TORCH_CHECK(Bq.sizes() == B.sizes() && Bq.stride(1) == 1 && B.stride(1) == 1, "sbr16_bq_out: shapes");
-  evx_sbr16_bq(B.data_ptr<float>(), (int)B.size(0), (int)n, B.stride(0), perm.data_ptr<int>(), Q.data_ptr<float>(), Bq.data_ptr<float>(),
-               Bq.stride(0), (int)sb, cur_stream(), skip.data_ptr<int>());
 }
 
 // X² stats partials (gemm_ks MODE 1 epilogue, double[4·nparts]) for the free ‖X‖ bound, may be absent
@@ -1639,8 +1564,6 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("gemm_ks_tile(int M, int N, int mode) -> int");
   m.def("cec_rotated_rowterms(Tensor X, Tensor Mrot, Tensor o, float alpha, int fid) -> Tensor");
   m.def("sbr16_block_out(Tensor A, int shift, int sweeps, int sb, Tensor(a!) perm, Tensor(b!) Q, Tensor(c!) dq, Tensor skip, float skip_tol=0.0) -> ()");
-  m.def("sbr16_far_out(Tensor A, Tensor perm, Tensor Q, Tensor dq, Tensor stats, float thr_fac, Tensor theta, Tensor(a!) X, int sb, Tensor skip) -> ()");
-  m.def("sbr16_bq_out(Tensor B, Tensor perm, Tensor Q, Tensor(a!) Bq, int sb, Tensor skip) -> ()");
   m.def("sbr_damping_out(Tensor X2, Tensor V, float tau, Tensor(a!) alpha, Tensor(b!) work, Tensor skip, Tensor(c!)? bar=None, bool no_final=False, Tensor? xpart=None) -> ()");
   m.def("sbr_dev_prep(Tensor X, Tensor X2, Tensor X3, Tensor(c!) alpha, Tensor(a!) P, Tensor(b!) MT, Tensor ctrl, Tensor? work=None, float tau=1.0, Tensor? xpart=None, Tensor? copy_src=None, Tensor(d!)? copy_dst=None, int minus_id=0) -> ()");
   m.def("sbr_dev_copy(Tensor src, Tensor(a!) dst, Tensor skip) -> ()");
@@ -1648,7 +1571,7 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("gemm_ks_set_tile(int t) -> ()");
   m.def("gemm_ks_set_prec(int prec) -> ()");
   m.def("gemm_ks_set_nw8(int tiles) -> ()");
-  m.def("gemm_ks_pl(Tensor? A, Tensor? a_pl, Tensor? B, Tensor? b_pl, int M, int N, int K, float alpha, Tensor? alpha_ptr, Tensor? bias_n, Tensor(a!)? out, Tensor? a_sub_k, int sub_cols=0, int sub_ld=0) -> Tensor");
+  m.def("gemm_ks_stacked(Tensor A, Tensor B, int M, int N, int K, float alpha, Tensor? alpha_ptr, Tensor? bias_n, Tensor(a!)? out, Tensor a_sub_k, int sub_cols, int sub_ld) -> Tensor");
   m.def("sbr16_far_bq_out(Tensor A, Tensor perm, Tensor Q, Tensor dq, Tensor stats, float thr_fac, Tensor theta, Tensor(a!) X, Tensor B, Tensor(b!) Bq, int sb, Tensor skip_far, Tensor skip_bq, bool pre=False) -> ()");
   m.def("lsmop_g(Tensor X, int[] start, int[] sublen, int[] func, int nk, int cosine) -> Tensor");
   m.def("cma_delta_gemv(Tensor M, Tensor mean, Tensor dm, float cm) -> Tensor[]");
@@ -1697,7 +1620,7 @@ TORCH_LIBRARY_IMPL(evoxmi, CompositeExplicitAutograd, m) {
   m.impl("gemm_ks_set_tile", &gemm_ks_set_tile);
   m.impl("gemm_ks_set_prec", &gemm_ks_set_prec);
   m.impl("gemm_ks_set_nw8", &gemm_ks_set_nw8);
-  m.impl("gemm_ks_pl", &gemm_ks_pl);
+  m.impl("gemm_ks_stacked", &gemm_ks_stacked);
   m.impl("sbr16_far_bq_out", &sbr16_far_bq_out);
   m.impl("gemm_ks_grid", &gemm_ks_grid);
   m.impl("gemm_ks_tile", &gemm_ks_tile);
@@ -1735,8 +1658,6 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("moead_halo_replace", &moead_halo_replace);
   m.impl("moead_halo_gather", &moead_halo_gather);
   m.impl("ipc_handle", &ipc_handle);
-  m.impl("sbr16_far_out", &sbr16_far_out);
-  m.impl("sbr16_bq_out", &sbr16_bq_out);
   m.impl("sbr_damping_out", &sbr_damping_out);
   m.impl("sbr_dev_prep", &sbr_dev_prep);
   m.impl("sbr_dev_copy", &sbr_dev_copy);

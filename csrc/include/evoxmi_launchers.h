@@ -70,12 +70,6 @@ struct EvxGemmKs {
   // Σ y² − 10 cos 2πy + 10 with y = 0.0512 z, 0), finished by evx_cec_rowterms_final
   float* row_terms;
   int row_fid;
-  // bf16x6 only: operands pre-split into fragment planes (evx_split_planes / evx_philox_normal_planes):
-  // uint16 [3][rows][kp] (h, m, l), kp = K rounded up to 32, each 32-k group in fragment order —
-  // the operand's f32 pointer is then not read (a K-contiguous operand of the same shape)
-  const uint16_t* a_pl;
-  const uint16_t* b_pl;
-  int64_t a_pl_rows, b_pl_rows, pl_kp;
   // per-column-block A shift (stacked products sharing A, e.g. the CEC'22 composition
   // rotations): output columns [c·sub_cols, (c+1)·sub_cols) use a_sub_k + c·sub_ld
   // (sub_cols a multiple of the tile width; 0: one shift for all columns)
@@ -134,8 +128,6 @@ void evx_philox_h3(const int64_t* key, int64_t rows, int d, int64_t row0, uint16
 void evx_gemm_h3(const EvxGemmBlk& a, hipStream_t s);
 // blocked planes of rows [row0, row0 + rows) of normal(key, (·, d)) (d % 4 == 0)
 void evx_philox_blk(const int64_t* key, int64_t rows, int d, int64_t row0, uint16_t* out, hipStream_t s);
-// fragment planes of X (rows × K, K-contiguous, row stride ld), X[r][k]·colscale[k] when colscale
-// fragment planes of rows [row0, row0 + rows) of the virtual normal matrix normal(key, (·, d)) (d % 4 == 0)
 int evx_gemm_ks_tiles_n(int M, int N, int mode);  // column tiles of a launch (row-terms partial count)
 void evx_cec_rowterms_final(const float* parts, int tiles_n, int M, int fid, float* out, hipStream_t s);
 // composition (F9–F12) in two launches: per part i the basic function fid[i] on z = Z[:, zcol[i] : +D]·scale[i]
@@ -158,7 +150,6 @@ void evx_gemm_ks_set_tile(int t);
 // 1: bf16x6 split products on the bf16 matrix pipe (default), 0: f32 MFMA
 void evx_gemm_ks_set_prec(int prec);
 void evx_gemm_ks_set_nw8(int tiles);  // 8-wave workgroups for grids of at most this many tiles
-int evx_gemm_ks_prec();
 void evx_cma_local_select(const int32_t* order, int mu, const float* w, int start, int size, int K, int32_t* rows, float* wk,
                           hipStream_t s);
 void evx_sym_pack(const float* S, int64_t lds, int d, float* P, hipStream_t s);

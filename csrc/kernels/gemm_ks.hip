@@ -56,15 +56,11 @@ namespace {
 // (v_mfma_f32_16x16x4_f32, 32 cycles for 1024 MACs), so six of them cost 3/8 of the f32
 // product; the split is ≈4.5 VALU instructions per operand element, co-issued with the
 // MFMAs of the previous block.
-#ifndef EVX_X6_SPLIT
-// 0: round-to-nearest parts (v_cvt_pk_bf16_f32, unbiased); 1: truncated parts (and / sub / perm):
-// 15 % fewer loop cycles but its dropped terms share the sign of a·b, so a same-sign sum (a
-// Gram diagonal over K = 5000) drifts past the f32 bound — measured, not used
-#define EVX_X6_SPLIT 0
-#endif
+// The parts are rounded to nearest (v_cvt_pk_bf16_f32, unbiased).  Truncated parts (and / sub /
+// perm) take 15 % fewer loop cycles, but their dropped terms share the sign of a·b, so a
+// same-sign sum (a Gram diagonal over K = 5000) drifts past the f32 bound: measured, not used.
 __device__ __forceinline__ void split3(const float4& v0, const float4& v1, bf16x8& h, bf16x8& m, bf16x8& l) {
   u32x4 H, M, L;
-#if EVX_X6_SPLIT == 0
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
     const float4& q = p < 2 ? v0 : v1;
@@ -81,28 +77,6 @@ __device__ __forceinline__ void split3(const float4& v0, const float4& v1, bf16x
     M[p] = __builtin_bit_cast(unsigned, mb);
     L[p] = __builtin_bit_cast(unsigned, lb);
   }
-#else
-  // truncated parts: h = the top 8 significand bits of a (mask), m = the top 8 of the exact
-  // remainder, l = what is left — at most 8 significant bits, so l is a bf16 exactly; every
-  // part is an f32 with a zero low half, packed pairwise with one byte permute
-  const float a[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-  unsigned hu[8], mu[8], lu[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const unsigned ab = __float_as_uint(a[c]);
-    hu[c] = ab & 0xFFFF0000u;
-    const float r1 = a[c] - __uint_as_float(hu[c]);
-    mu[c] = __float_as_uint(r1) & 0xFFFF0000u;
-    lu[c] = __float_as_uint(r1 - __uint_as_float(mu[c]));
-  }
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    // high halves of (x0, x1) → one dword (x1 in the high half)
-    H[p] = __builtin_amdgcn_perm(hu[2 * p + 1], hu[2 * p], 0x07060302u);
-    M[p] = __builtin_amdgcn_perm(mu[2 * p + 1], mu[2 * p], 0x07060302u);
-    L[p] = __builtin_amdgcn_perm(lu[2 * p + 1], lu[2 * p], 0x07060302u);
-  }
-#endif
   h = __builtin_bit_cast(bf16x8, H);
   m = __builtin_bit_cast(bf16x8, M);
   l = __builtin_bit_cast(bf16x8, L);
@@ -252,15 +226,10 @@ __device__ __forceinline__ void decode_tile(int bid, int tiles_m, int tiles_n, i
 // NW: waves per workgroup, each owning 1/NW of K.  8 for grids that cannot fill the chip twice
 // (the 1000³ eigensolver products: 256 tiles for 256 CUs): two waves per SIMD, so one wave's loads
 // are in flight while the other computes; the first 4 waves then run the 4-wave epilogue.
-// PL (operands as pre-split bf16x6 fragment planes) is no longer launched: the round-4 opt-in
-// measured no gain inside the generation (profiles/NOTES.md); the template keeps PL = 0.
-template <int TM, int TN, int KH, bool AKC, bool BKC, int MODE, int PREC, int PL = 0, int NW = 4>
+template <int TM, int TN, int KH, bool AKC, bool BKC, int MODE, int PREC, int NW = 4>
 __global__ void __launch_bounds__(64 * NW) gemm_ks_kernel(EvxGemmKs p) {
   static_assert(NW == 4 || NW == 8, "4 or 8 waves");
   static_assert(PREC == 0 || KH == 2, "bf16x6 groups hold two float4 per lane and block");
-  static_assert(PL == 0 || (PREC == 1 && AKC && BKC), "fragment planes: bf16x6 on 16x16x32, K-contiguous operands");
-  static_assert(PREC != 3 || PL == 0, "bf16x3 splits in registers");
-  constexpr bool APL = PL & 1, BPL = PL & 2;
   static_assert(PREC != 2 || (TM % 2 == 0 && TN % 2 == 0), "32x32 MFMA tiles need even 16-blocks");
   if (p.skip && *p.skip) return;
   if (p.sel && *p.sel) {
@@ -312,21 +281,6 @@ __global__ void __launch_bounds__(64 * NW) gemm_ks_kernel(EvxGemmKs p) {
     bp[j] = BKC ? p.B + (int64_t)col * p.ldb : p.B + col;
   }
 
-  // fragment-plane operands: lane (r, q) reads the 16 bytes of its 8 k values of a 32-k group at
-  // plane[row][32·group + 8q] (h, m and l planes 3 × 16 B apart by a plane stride)
-  const uint16_t* apl[APL ? NA : 1];
-  const uint16_t* bpl[BPL ? NB : 1];
-  const int64_t pl_kp = p.pl_kp;
-  if constexpr (APL) {
-#pragma unroll
-    for (int i = 0; i < NA; ++i) apl[i] = p.a_pl + (int64_t)min(m0 + RB * i + rl, p.M - 1) * pl_kp + 8 * q;
-  }
-  if constexpr (BPL) {
-#pragma unroll
-    for (int j = 0; j < NB; ++j) bpl[j] = p.b_pl + (int64_t)min(n0 + RB * j + rl, p.N - 1) * pl_kp + 8 * q;
-  }
-  const int64_t a_plane = (int64_t)p.a_pl_rows * pl_kp, b_plane = (int64_t)p.b_pl_rows * pl_kp;
-
   using AccT = typename std::conditional<PREC == 2, f32x16, f32x4>::type;
   AccT acc[NA][NB];
 #pragma unroll
@@ -338,14 +292,13 @@ __global__ void __launch_bounds__(64 * NW) gemm_ks_kernel(EvxGemmKs p) {
 
   // loads per slot: one float4 (KC) or four dwords (RC) per block and float4 slot; at most
   // 63 vector loads can be counted in flight (vmcnt)
-  constexpr int LPS = KH * (NA * (AKC ? 1 : 4) + NB * (BKC ? 1 : 4)) + (APL ? NA : 0) + (BPL ? NB : 0);
+  constexpr int LPS = KH * (NA * (AKC ? 1 : 4) + NB * (BKC ? 1 : 4));
 #ifdef EVX_KS_DEPTH  // tools/gemm_ks_probe.cpp experiments
   constexpr int D = EVX_KS_DEPTH;
 #else
   constexpr int D = (3 * LPS <= 63) ? 3 : 2;
 #endif
-  float4 fa[D][KH][APL ? 1 : NA], fb[D][KH][BPL ? 1 : NB];
-  uint4 pa[D][3][APL ? NA : 1], pb[D][3][BPL ? NB : 1];
+  float4 fa[D][KH][NA], fb[D][KH][NB];
   const int64_t lda = p.lda, ldb = p.ldb;
   // k of float4 h of a lane: PREC 0/1: KG·group + 16h + 4q + c (lane (r, q));
   // PREC 2: KG·group + 8·hw + 4h + c (lane (rw, hw)) — the same map for A and B, so the
@@ -355,38 +308,19 @@ __global__ void __launch_bounds__(64 * NW) gemm_ks_kernel(EvxGemmKs p) {
   // values rides along with the operand loads, the subtraction runs just before the MFMAs
   const float* __restrict__ asub = (p.a_sub_k && p.sub_cols > 0) ? p.a_sub_k + (int64_t)(n0 / p.sub_cols) * p.sub_ld : p.a_sub_k;
   float4 fs[D][KH];
-  constexpr int NAF = APL ? 1 : NA, NBF = BPL ? 1 : NB;
-  auto load_slot = [&](float4 (&xa)[KH][NAF], float4 (&xb)[KH][NBF], float4 (&xs)[KH], uint4 (&ya)[3][APL ? NA : 1],
-                       uint4 (&yb)[3][BPL ? NB : 1], int grp) {
+  auto load_slot = [&](float4 (&xa)[KH][NA], float4 (&xb)[KH][NB], float4 (&xs)[KH], int grp) {
 #pragma unroll
     for (int h = 0; h < KH; ++h) {
       const int k = kof(grp, h);
-      if (AKC && asub && !APL) xs[h] = *reinterpret_cast<const float4*>(asub + k);
-      if constexpr (!APL) {
+      if (AKC && asub) xs[h] = *reinterpret_cast<const float4*>(asub + k);
 #pragma unroll
-        for (int i = 0; i < NA; ++i) xa[h][i] = load_full<AKC>(ap[i], lda, k);
-      }
-      if constexpr (!BPL) {
+      for (int i = 0; i < NA; ++i) xa[h][i] = load_full<AKC>(ap[i], lda, k);
 #pragma unroll
-        for (int j = 0; j < NB; ++j) xb[h][j] = load_full<BKC>(bp[j], ldb, k);
-      }
-    }
-    if constexpr (APL) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int i = 0; i < NA; ++i) ya[c][i] = *reinterpret_cast<const uint4*>(apl[i] + c * a_plane + 32 * grp);
-    }
-    if constexpr (BPL) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) yb[c][j] = *reinterpret_cast<const uint4*>(bpl[j] + c * b_plane + 32 * grp);
+      for (int j = 0; j < NB; ++j) xb[h][j] = load_full<BKC>(bp[j], ldb, k);
     }
   };
-  auto compute_slot = [&](float4 (&xa)[KH][NAF], const float4 (&xb)[KH][NBF], const float4 (&xs)[KH], const uint4 (&ya)[3][APL ? NA : 1],
-                          const uint4 (&yb)[3][BPL ? NB : 1]) {
-    if (AKC && asub && !APL) {
+  auto compute_slot = [&](float4 (&xa)[KH][NA], const float4 (&xb)[KH][NB], const float4 (&xs)[KH]) {
+    if (AKC && asub) {
 #pragma unroll
       for (int h = 0; h < KH; ++h)
 #pragma unroll
@@ -411,25 +345,11 @@ __global__ void __launch_bounds__(64 * NW) gemm_ks_kernel(EvxGemmKs p) {
     } else if constexpr (PREC >= 1) {
       bf16x8 bh[NB], bm[NB], bl[NB];
 #pragma unroll
-      for (int j = 0; j < NB; ++j) {
-        if constexpr (BPL) {
-          bh[j] = __builtin_bit_cast(bf16x8, yb[0][j]);
-          bm[j] = __builtin_bit_cast(bf16x8, yb[1][j]);
-          bl[j] = __builtin_bit_cast(bf16x8, yb[2][j]);
-        } else {
-          split3(xb[0][BPL ? 0 : j], xb[1][BPL ? 0 : j], bh[j], bm[j], bl[j]);
-        }
-      }
+      for (int j = 0; j < NB; ++j) split3(xb[0][j], xb[1][j], bh[j], bm[j], bl[j]);
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
         bf16x8 ah, am, al;
-        if constexpr (APL) {
-          ah = __builtin_bit_cast(bf16x8, ya[0][i]);
-          am = __builtin_bit_cast(bf16x8, ya[1][i]);
-          al = __builtin_bit_cast(bf16x8, ya[2][i]);
-        } else {
-          split3(xa[0][APL ? 0 : i], xa[1][APL ? 0 : i], ah, am, al);
-        }
+        split3(xa[0][i], xa[1][i], ah, am, al);
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
           if constexpr (PREC == 2) acc[i][j] = mfma_x6w(ah, am, al, bh[j], bm[j], bl[j], acc[i][j]);
@@ -445,7 +365,7 @@ __global__ void __launch_bounds__(64 * NW) gemm_ks_kernel(EvxGemmKs p) {
           for (int i = 0; i < NA; ++i)
 #pragma unroll
             for (int j = 0; j < NB; ++j)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32((&xa[h][APL ? 0 : i].x)[e], (&xb[h][BPL ? 0 : j].x)[e], acc[i][j], 0, 0, 0);
+              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32((&xa[h][i].x)[e], (&xb[h][j].x)[e], acc[i][j], 0, 0, 0);
     }
   };
   // Loads are issued unconditionally (group index clamped to the wave's last group, so the
@@ -457,7 +377,7 @@ __global__ void __launch_bounds__(64 * NW) gemm_ks_kernel(EvxGemmKs p) {
   const int glast = max(g1 - 1, g0);
   if (ngf > 0) {
 #pragma unroll
-    for (int s = 0; s < D - 1; ++s) load_slot(fa[s], fb[s], fs[s], pa[s], pb[s], min(g0 + s, glast));
+    for (int s = 0; s < D - 1; ++s) load_slot(fa[s], fb[s], fs[s], min(g0 + s, glast));
   }
   // chunks of D groups with no branch inside (load group g + s + D − 1, compute group g + s),
   // then the < D remaining groups, whose data the last chunk (or the prologue) loaded
@@ -467,50 +387,33 @@ __global__ void __launch_bounds__(64 * NW) gemm_ks_kernel(EvxGemmKs p) {
     for (int s = 0; s < D; ++s) {
 #ifndef EVX_KS_NO_LOADS  // probe: MFMA loop alone (operands of the prologue reused)
 #ifdef EVX_KS_FAKE_LOADS  // probe: every group re-reads group g0 (L1-resident operands)
-      load_slot(fa[(s + D - 1) % D], fb[(s + D - 1) % D], fs[(s + D - 1) % D], pa[(s + D - 1) % D], pb[(s + D - 1) % D], g0);
+      load_slot(fa[(s + D - 1) % D], fb[(s + D - 1) % D], fs[(s + D - 1) % D], g0);
 #else
-      load_slot(fa[(s + D - 1) % D], fb[(s + D - 1) % D], fs[(s + D - 1) % D], pa[(s + D - 1) % D], pb[(s + D - 1) % D],
-                min(g + s + D - 1, glast));
+      load_slot(fa[(s + D - 1) % D], fb[(s + D - 1) % D], fs[(s + D - 1) % D], min(g + s + D - 1, glast));
 #endif
 #endif
       // keep the issue order (loads of group g + s + D − 1 before the MFMAs of group g + s):
       // left alone, the scheduler sinks the loads behind the MFMAs and the prefetch distance
       // collapses to one group
       __builtin_amdgcn_sched_barrier(0);
-      compute_slot(fa[s], fb[s], fs[s], pa[s], pb[s]);
+      compute_slot(fa[s], fb[s], fs[s]);
       __builtin_amdgcn_sched_barrier(0);
     }
   }
 #pragma unroll
   for (int s = 0; s < D - 1; ++s)
-    if (g + s < g1) compute_slot(fa[s], fb[s], fs[s], pa[s], pb[s]);
-  if (w == 0 && K % KG) {  // tail (masked loads; fragment planes are zero-padded to kp)
+    if (g + s < g1) compute_slot(fa[s], fb[s], fs[s]);
+  if (w == 0 && K % KG) {  // tail (masked loads)
 #pragma unroll
     for (int h = 0; h < KH; ++h) {
       const int k = kof(ngf, h);
-      if (AKC && asub && !APL) fs[0][h] = load_tail<true>(asub, 0, k, K);
-      if constexpr (!APL) {
+      if (AKC && asub) fs[0][h] = load_tail<true>(asub, 0, k, K);
 #pragma unroll
-        for (int i = 0; i < NA; ++i) fa[0][h][i] = load_tail<AKC>(ap[i], lda, k, K);
-      }
-      if constexpr (!BPL) {
+      for (int i = 0; i < NA; ++i) fa[0][h][i] = load_tail<AKC>(ap[i], lda, k, K);
 #pragma unroll
-        for (int j = 0; j < NB; ++j) fb[0][h][j] = load_tail<BKC>(bp[j], ldb, k, K);
-      }
+      for (int j = 0; j < NB; ++j) fb[0][h][j] = load_tail<BKC>(bp[j], ldb, k, K);
     }
-    if constexpr (APL) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int i = 0; i < NA; ++i) pa[0][c][i] = *reinterpret_cast<const uint4*>(apl[i] + c * a_plane + 32 * ngf);
-    }
-    if constexpr (BPL) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) pb[0][c][j] = *reinterpret_cast<const uint4*>(bpl[j] + c * b_plane + 32 * ngf);
-    }
-    compute_slot(fa[0], fb[0], fs[0], pa[0], pb[0]);
+    compute_slot(fa[0], fb[0], fs[0]);
   }
 
   // ---- epilogue: sum the four K-partials through LDS, pairwise: waves 2, 3 park theirs,
@@ -741,10 +644,10 @@ template <int TM, int TN, int MODE, int PREC, int NW>
 void launch_prec_nw(const EvxGemmKs& a, int tiles, hipStream_t s) {
   constexpr int KH = PREC >= 1 ? 2 : EVX_KS_KH;
   const dim3 grid(tiles), block(64 * NW);
-  if (a.a_kc && a.b_kc) gemm_ks_kernel<TM, TN, KH, true, true, MODE, PREC, 0, NW><<<grid, block, 0, s>>>(a);
-  else if (a.a_kc && !a.b_kc) gemm_ks_kernel<TM, TN, KH, true, false, MODE, PREC, 0, NW><<<grid, block, 0, s>>>(a);
-  else if (!a.a_kc && a.b_kc) gemm_ks_kernel<TM, TN, KH, false, true, MODE, PREC, 0, NW><<<grid, block, 0, s>>>(a);
-  else gemm_ks_kernel<TM, TN, KH, false, false, MODE, PREC, 0, NW><<<grid, block, 0, s>>>(a);
+  if (a.a_kc && a.b_kc) gemm_ks_kernel<TM, TN, KH, true, true, MODE, PREC, NW><<<grid, block, 0, s>>>(a);
+  else if (a.a_kc && !a.b_kc) gemm_ks_kernel<TM, TN, KH, true, false, MODE, PREC, NW><<<grid, block, 0, s>>>(a);
+  else if (!a.a_kc && a.b_kc) gemm_ks_kernel<TM, TN, KH, false, true, MODE, PREC, NW><<<grid, block, 0, s>>>(a);
+  else gemm_ks_kernel<TM, TN, KH, false, false, MODE, PREC, NW><<<grid, block, 0, s>>>(a);
 }
 
 // 8-wave workgroups for grids of at most this many tiles whose K gives every wave ≥ 12 k-groups
@@ -792,8 +695,6 @@ void evx_gemm_ks_set_tile(int t) { g_ks_tile_override = t; }
 void evx_gemm_ks_set_prec(int prec) { g_ks_prec = prec; }
 
 void evx_gemm_ks_set_nw8(int tiles) { g_ks_nw8_tiles = tiles; }
-
-int evx_gemm_ks_prec() { return g_ks_prec; }
 
 int evx_gemm_ks_tile(int M, int N, int mode) { return evx_host::gemm_ks_tile(M, N, mode, g_ks_tile_override); }
 

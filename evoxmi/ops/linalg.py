@@ -238,8 +238,8 @@ def mm_nt(A, B, *, alpha: float = 1.0, alpha_ptr: Optional[torch.Tensor] = None,
             blocks = [((A - a_sub_k[c][None, :]) @ B[c * sub_cols : (c + 1) * sub_cols].T) for c in range(a_sub_k.shape[0])]
             C = alpha * torch.cat(blocks, 1)[:, : B.shape[0]]
             return C if alpha_ptr is None else C * alpha_ptr.reshape(())
-        return _ext.ops().gemm_ks_pl(A, None, B, None, int(A.shape[0]), int(B.shape[0]), int(A.shape[1]), float(alpha), alpha_ptr, bias_n,
-                                     out, a_sub_k.contiguous(), int(sub_cols), int(a_sub_k.stride(0)))
+        return _ext.ops().gemm_ks_stacked(A, B, int(A.shape[0]), int(B.shape[0]), int(A.shape[1]), float(alpha), alpha_ptr, bias_n, out,
+                                          a_sub_k.contiguous(), int(sub_cols), int(a_sub_k.stride(0)))
     return mm(A, B, tb=True, alpha=alpha, alpha_ptr=alpha_ptr, bias_n=bias_n, out=out, a_sub_k=a_sub_k)
 
 

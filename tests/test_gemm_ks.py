@@ -150,22 +150,49 @@ def test_gemm_ks_fused_shift_prologue(M, N, K):
     assert bool((Z0 == 0).all())
 
 
-@pytest.mark.gpu
-def test_gemm_per_block_shifts():
-    """Stacked shifted products in one launch: column block c uses shift row c (exact zero when
-    a row equals its block's shift)."""
-    g = torch.Generator().manual_seed(9)
-    M, K, blocks, W = 3000, 1000, 3, 1024
+def _per_block_shifts(M, K, blocks, W, seed):
+    """mm_nt with one shift row per W-wide column block against float64; row 5 equals block 1's
+    shift, so its block-1 outputs are exact zeros.  Returns the device operands and result."""
+    g = torch.Generator().manual_seed(seed)
     X = torch.randn(M, K, generator=g)
     Bs = torch.randn(blocks * W, K, generator=g)
     O = torch.randn(blocks, K, generator=g)
     X[5] = O[1]
-    Z = linalg.mm_nt(X.cuda(), Bs.cuda(), a_sub_k=O.cuda(), sub_cols=W).cpu().double()
+    Xd, Bd, Od = X.cuda(), Bs.cuda(), O.cuda()
+    Zd = linalg.mm_nt(Xd, Bd, a_sub_k=Od, sub_cols=W)
+    Z = Zd.cpu().double()
     for c in range(blocks):
         ref = (X.double() - O[c].double()) @ Bs[c * W : (c + 1) * W].double().t()
         tol = 2e-6 * ((X - O[c]).double().abs() @ Bs[c * W : (c + 1) * W].double().abs().t())
         assert ((Z[:, c * W : (c + 1) * W] - ref).abs() <= tol + 1e-30).all(), c
     assert bool((Z[5, W : 2 * W] == 0).all())
+    return Xd, Bd, Od, Zd
+
+
+@pytest.mark.gpu
+def test_gemm_per_block_shifts():
+    """Stacked shifted products in one launch: column block c uses shift row c (exact zero when
+    a row equals its block's shift)."""
+    _per_block_shifts(3000, 1000, 3, 1024, seed=9)
+
+
+@pytest.mark.gpu
+def test_gemm_per_block_shifts_forced_tile():
+    """Stacked shifted products where the shape heuristic's tile does not divide the block width:
+    at 768 × 768 it picks the 48-wide tile (one round of 256 tiles), 256 is no multiple of 48, so
+    the op must launch 64-wide tiles instead.  K = 36 leaves a masked tail group.  The same
+    product written through ``out=`` into a column slice of a wider buffer is bit-equal and
+    leaves the other columns alone."""
+    from evoxmi.ops import _ext
+
+    M, W, off = 768, 256, 128
+    N = 3 * W
+    assert int(_ext.ops().gemm_ks_tile(M, N, 0)) == 3
+    Xd, Bd, Od, Zd = _per_block_shifts(M, 36, 3, W, seed=11)
+    wide = torch.full((M, N + 2 * off), 123.0, device="cuda")
+    linalg.mm_nt(Xd, Bd, a_sub_k=Od, sub_cols=W, out=wide[:, off : off + N])
+    assert torch.equal(wide[:, off : off + N], Zd)
+    assert bool((wide[:, :off] == 123.0).all()) and bool((wide[:, off + N :] == 123.0).all())
 
 
 @pytest.mark.gpu
