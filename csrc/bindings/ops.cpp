@@ -1459,6 +1459,38 @@ std::vector<at::Tensor> sra_indicators(const at::Tensor& obj) {
   return {I1, I2};
 }
 
+std::vector<at::Tensor> ibea_fitness(const at::Tensor& obj, double kappa) {
+  CHECK_DEV(obj); CHECK_F32(obj); CHECK_CONTIG(obj);
+  TORCH_CHECK(obj.dim() == 2, "ibea_fitness: obj float32 (n, m)");
+  const int64_t n = obj.size(0), m = obj.size(1);
+  TORCH_CHECK(m >= 1 && m <= evx_ibea_max_m(), "ibea_fitness: 1 <= m <= ", evx_ibea_max_m());
+  TORCH_CHECK(n <= (1 << 24), "ibea_fitness: n <= 2^24");
+  c10::DeviceGuard g(obj.device());
+  auto f = at::empty({n}, obj.options()), C = at::empty({n}, obj.options());
+  evx_ibea_fitness(obj.data_ptr<float>(), (int)n, (int)m, (float)kappa, f.data_ptr<float>(), C.data_ptr<float>(), cur_stream());
+  return {f, C};
+}
+
+std::vector<at::Tensor> ibea_truncate(const at::Tensor& obj, const at::Tensor& f, const at::Tensor& C, double kappa, int64_t n_remove,
+                                      int64_t n_keep) {
+  CHECK_DEV(obj); CHECK_F32(obj); CHECK_CONTIG(obj); CHECK_DEV(f); CHECK_F32(f); CHECK_CONTIG(f);
+  CHECK_DEV(C); CHECK_F32(C); CHECK_CONTIG(C);
+  TORCH_CHECK(obj.dim() == 2, "ibea_truncate: obj float32 (n, m)");
+  const int64_t n = obj.size(0), m = obj.size(1);
+  TORCH_CHECK(f.dim() == 1 && C.dim() == 1 && f.numel() == n && C.numel() == n, "ibea_truncate: f, C float32 (n,)");
+  TORCH_CHECK(n >= 1 && n <= evx_ibea_max_n(), "ibea_truncate: 1 <= n <= ", evx_ibea_max_n());
+  TORCH_CHECK(m >= 1 && m <= evx_ibea_max_m(), "ibea_truncate: 1 <= m <= ", evx_ibea_max_m());
+  TORCH_CHECK(n_remove >= 0 && n_remove <= n, "ibea_truncate: need 0 <= n_remove <= n");
+  TORCH_CHECK(n_keep >= 0 && n_keep <= n - n_remove, "ibea_truncate: need 0 <= n_keep <= n - n_remove");
+  TORCH_CHECK(f.device() == obj.device() && C.device() == obj.device(), "ibea_truncate: one device");
+  c10::DeviceGuard g(obj.device());
+  auto idx = at::empty({n_keep}, obj.options().dtype(at::kLong)), order = at::empty({n_remove}, obj.options().dtype(at::kLong));
+  const at::Tensor objT = obj.t().contiguous();  // (m, n): a thread's rows are n-strided, its loads coalesced
+  evx_ibea_truncate(objT.data_ptr<float>(), f.data_ptr<float>(), C.data_ptr<float>(), (float)kappa, (int)n, (int)m, (int)n_remove,
+                    (int)n_keep, idx.data_ptr<int64_t>(), order.data_ptr<int64_t>(), cur_stream());
+  return {idx, order};
+}
+
 }  // namespace
 
 // OpenES gradient with Philox-regenerated noise: g[j] = Σ_i w[i] ε(row0 + i, j)
@@ -1586,6 +1618,8 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("nsga3_niche_select(Tensor rank, Tensor last_rank, Tensor group, Tensor group_dist, Tensor key, int N, int R) -> Tensor");
   m.def("sra_rank(Tensor I1, Tensor I2, Tensor u, Tensor pc) -> Tensor");
   m.def("sra_indicators(Tensor obj) -> Tensor[]");
+  m.def("ibea_fitness(Tensor obj_norm, float kappa) -> Tensor[]");
+  m.def("ibea_truncate(Tensor obj_norm, Tensor f, Tensor C, float kappa, int n_remove, int n_keep) -> Tensor[]");
   m.def("moead_parents(Tensor nb, Tensor key, int row0=0, int rows=0) -> Tensor[]");
   m.def("moead_variation(Tensor pop, Tensor p0, Tensor p1, Tensor kx, Tensor km, Tensor lb, Tensor ub, float pro_c, float dis_c, float pro_m, float dis_m, int nm, int row0=0, int rows=0, Tensor? win=None, Tensor(a!)? out=None) -> Tensor");
   m.def("moead_halo_replace(Tensor(a!) obj, Tensor off_obj, Tensor W, Tensor z, Tensor zmax, Tensor rowptr, Tensor owner, Tensor slots, int func, Tensor(b!) win_h) -> ()");
@@ -1676,6 +1710,8 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("nsga3_niche_select", &nsga3_niche_select);
   m.impl("sra_rank", &sra_rank);
   m.impl("sra_indicators", &sra_indicators);
+  m.impl("ibea_fitness", &ibea_fitness);
+  m.impl("ibea_truncate", &ibea_truncate);
   m.impl("moead_parents", &moead_parents);
   m.impl("moead_variation", &moead_variation);
   m.impl("moead_replace", &moead_replace);

@@ -240,6 +240,13 @@ int evx_sra_rank_max_n();
 int evx_sra_indicators_max_m();
 void evx_sra_rank(const float* I1, const float* I2, const float* u, const float* pc, int n, int64_t* rank, hipStream_t s);
 void evx_sra_indicators(const float* obj, int n, int m, float* I1, float* I2, hipStream_t s);
+// ibea_select.hip: IBEA's I_ε+ fitness (f, C of the normalised objectives, m ≤ evx_ibea_max_m()) and its truncation
+// (objT the (m, n) transpose, n ≤ evx_ibea_max_n(), n_keep ≤ n − n_remove; idx (n_keep,) ascending survivors, order (n_remove,) the removed rows)
+int evx_ibea_max_n();
+int evx_ibea_max_m();
+void evx_ibea_fitness(const float* obj, int n, int m, float kappa, float* f, float* C, hipStream_t s);
+void evx_ibea_truncate(const float* objT, const float* f, const float* C, float kappa, int n, int m, int n_remove, int n_keep,
+                       int64_t* idx, int64_t* order, hipStream_t s);
 // sorted-block refinement of a warm-started eigendecomposition (eigh_sbr.hip, evoxmi/ops/sbr.py)
 int evx_sbr_nblocks(int n, int off);
 int evx_sbr_stat_parts();

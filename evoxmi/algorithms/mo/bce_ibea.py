@@ -15,9 +15,9 @@ import torch
 from ...core import State
 from ...operators import crossover, selection
 from ...operators.selection.non_dominate import non_dominated_sort
+from ...ops import ibea as ibea_ops
 from ...ops import random as rnd
 from .common import MOAlgorithm
-from .ibea import cal_fitness, ibea_truncate
 
 
 def exploration(pc_obj, npc_obj, n_nd, n):
@@ -60,9 +60,7 @@ def pc_selection(pc, pc_obj, n):
 
 
 def ibea_selection(pop, obj, n, kappa):
-    f, I, C = cal_fitness(obj, kappa)
-    keep = ibea_truncate(f, I, C, kappa, obj.shape[0] - n)
-    idx = torch.argsort((~keep).to(torch.int64), stable=True)[:n]
+    idx = ibea_ops.select(obj, kappa, n)
     return pop[idx], obj[idx]
 
 
@@ -86,7 +84,7 @@ class BCEIBEA(MOAlgorithm):
         key, k1, x_key, mut_key = rnd.split(state.key, 4)
         N = self.pop_size
         if state.counter % 2 == 0:  # IBEA variation on NPC
-            fit = -cal_fitness(state.npc_obj, self.kappa)[0]
+            fit = -ibea_ops.fitness(state.npc_obj, self.kappa)[0]
             selected, _ = self.selection(k1, state.npc, fit)
             off = self.mutation(mut_key, self.crossover(x_key, selected))
         else:  # PC exploration
