@@ -1491,6 +1491,61 @@ std::vector<at::Tensor> ibea_truncate(const at::Tensor& obj, const at::Tensor& f
   return {idx, order};
 }
 
+// sig, S, R, D, nd, msk, nn_d2, nn_idx of spea2_select.hip's two fitness launches
+std::vector<at::Tensor> spea2_fitness(const at::Tensor& obj) {
+  CHECK_DEV(obj); CHECK_F32(obj); CHECK_CONTIG(obj);
+  TORCH_CHECK(obj.dim() == 2, "spea2_fitness: obj float32 (n, m)");
+  const int64_t n = obj.size(0), m = obj.size(1);
+  TORCH_CHECK(m >= 1 && m <= evx_spea2_max_m(), "spea2_fitness: 1 <= m <= ", evx_spea2_max_m());
+  TORCH_CHECK(n >= 1 && n <= evx_spea2_fitness_max_n(), "spea2_fitness: 1 <= n <= ", evx_spea2_fitness_max_n());
+  c10::DeviceGuard g(obj.device());
+  const auto f = obj.options(), i32 = obj.options().dtype(at::kInt), b8 = obj.options().dtype(at::kBool);
+  auto S = at::empty({n}, i32), nn_idx = at::empty({n}, i32), nd = at::empty({n}, b8), msk = at::empty({n}, b8);
+  auto D = at::empty({n}, f), R = at::empty({n}, f), sig = at::empty({n}, f), nn_d2 = at::empty({n}, f);
+  evx_spea2_fitness(obj.data_ptr<float>(), (int)n, (int)m, S.data_ptr<int32_t>(), (uint8_t*)nd.data_ptr<bool>(),
+                    (uint8_t*)msk.data_ptr<bool>(), D.data_ptr<float>(), R.data_ptr<float>(), sig.data_ptr<float>(),
+                    nn_d2.data_ptr<float>(), nn_idx.data_ptr<int32_t>(), cur_stream());
+  return {sig, S, R, D, nd, msk, nn_d2, nn_idx};
+}
+
+// keep, order, {rescans, removed}; without (nn_d2, nn_idx) the neighbour pass runs first for the given mask
+std::vector<at::Tensor> spea2_truncate(const at::Tensor& obj, const at::Tensor& mask, int64_t n_keep,
+                                       const c10::optional<at::Tensor>& nn_d2, const c10::optional<at::Tensor>& nn_idx) {
+  CHECK_DEV(obj); CHECK_F32(obj); CHECK_CONTIG(obj); CHECK_DEV(mask); CHECK_CONTIG(mask);
+  TORCH_CHECK(obj.dim() == 2, "spea2_truncate: obj float32 (n, m)");
+  const int64_t n = obj.size(0), m = obj.size(1);
+  TORCH_CHECK(mask.scalar_type() == at::kBool && mask.dim() == 1 && mask.numel() == n, "spea2_truncate: mask bool (n,)");
+  TORCH_CHECK(n >= 1 && n <= evx_spea2_max_n(), "spea2_truncate: 1 <= n <= ", evx_spea2_max_n());
+  TORCH_CHECK(m >= 1 && m <= evx_spea2_max_m(), "spea2_truncate: 1 <= m <= ", evx_spea2_max_m());
+  TORCH_CHECK(n_keep >= 1, "spea2_truncate: need n_keep >= 1");
+  TORCH_CHECK(mask.device() == obj.device(), "spea2_truncate: one device");
+  TORCH_CHECK(nn_d2.has_value() == nn_idx.has_value(), "spea2_truncate: nn_d2 and nn_idx come together");
+  c10::DeviceGuard g(obj.device());
+  at::Tensor d2v, idxv;
+  if (nn_d2.has_value()) {
+    d2v = *nn_d2;
+    idxv = *nn_idx;
+    CHECK_DEV(d2v); CHECK_F32(d2v); CHECK_CONTIG(d2v); CHECK_DEV(idxv); CHECK_CONTIG(idxv);
+    TORCH_CHECK(d2v.dim() == 1 && d2v.numel() == n, "spea2_truncate: nn_d2 float32 (n,)");
+    TORCH_CHECK(idxv.scalar_type() == at::kInt && idxv.dim() == 1 && idxv.numel() == n, "spea2_truncate: nn_idx int32 (n,)");
+    TORCH_CHECK(d2v.device() == obj.device() && idxv.device() == obj.device(), "spea2_truncate: one device");
+  } else {
+    d2v = at::empty({n}, obj.options());
+    idxv = at::empty({n}, obj.options().dtype(at::kInt));
+    evx_spea2_neighbours(obj.data_ptr<float>(), (int)n, (int)m, (const uint8_t*)mask.data_ptr<bool>(), d2v.data_ptr<float>(),
+                         idxv.data_ptr<int32_t>(), cur_stream());
+  }
+  const int64_t M = evx_spea2_padded_m((int)m), n_order = std::max<int64_t>(n - n_keep, 0);
+  auto objT = at::zeros({M, n}, obj.options());  // (M, n): a thread's rows are n-strided, its loads coalesced; zero rows add nothing to d2
+  objT.narrow(0, 0, m).copy_(obj.t());
+  auto keep = at::empty({n}, obj.options().dtype(at::kBool)), order = at::empty({n_order}, obj.options().dtype(at::kLong));
+  auto stats = at::empty({2}, obj.options().dtype(at::kInt));
+  evx_spea2_truncate(objT.data_ptr<float>(), (int)n, (int)M, (const uint8_t*)mask.data_ptr<bool>(), d2v.data_ptr<float>(),
+                     idxv.data_ptr<int32_t>(), (int)n_keep, (uint8_t*)keep.data_ptr<bool>(), order.data_ptr<int64_t>(), (int)n_order,
+                     stats.data_ptr<int32_t>(), cur_stream());
+  return {keep, order, stats};
+}
+
 }  // namespace
 
 // OpenES gradient with Philox-regenerated noise: g[j] = Σ_i w[i] ε(row0 + i, j)
@@ -1620,6 +1675,8 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("sra_indicators(Tensor obj) -> Tensor[]");
   m.def("ibea_fitness(Tensor obj_norm, float kappa) -> Tensor[]");
   m.def("ibea_truncate(Tensor obj_norm, Tensor f, Tensor C, float kappa, int n_remove, int n_keep) -> Tensor[]");
+  m.def("spea2_fitness(Tensor obj) -> Tensor[]");
+  m.def("spea2_truncate(Tensor obj, Tensor mask, int n_keep, Tensor? nn_d2, Tensor? nn_idx) -> Tensor[]");
   m.def("moead_parents(Tensor nb, Tensor key, int row0=0, int rows=0) -> Tensor[]");
   m.def("moead_variation(Tensor pop, Tensor p0, Tensor p1, Tensor kx, Tensor km, Tensor lb, Tensor ub, float pro_c, float dis_c, float pro_m, float dis_m, int nm, int row0=0, int rows=0, Tensor? win=None, Tensor(a!)? out=None) -> Tensor");
   m.def("moead_halo_replace(Tensor(a!) obj, Tensor off_obj, Tensor W, Tensor z, Tensor zmax, Tensor rowptr, Tensor owner, Tensor slots, int func, Tensor(b!) win_h) -> ()");
@@ -1712,6 +1769,8 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("sra_indicators", &sra_indicators);
   m.impl("ibea_fitness", &ibea_fitness);
   m.impl("ibea_truncate", &ibea_truncate);
+  m.impl("spea2_fitness", &spea2_fitness);
+  m.impl("spea2_truncate", &spea2_truncate);
   m.impl("moead_parents", &moead_parents);
   m.impl("moead_variation", &moead_variation);
   m.impl("moead_replace", &moead_replace);

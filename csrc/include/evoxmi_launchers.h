@@ -247,6 +247,19 @@ int evx_ibea_max_m();
 void evx_ibea_fitness(const float* obj, int n, int m, float kappa, float* f, float* C, hipStream_t s);
 void evx_ibea_truncate(const float* objT, const float* f, const float* C, float kappa, int n, int m, int n_remove, int n_keep,
                        int64_t* idx, int64_t* order, hipStream_t s);
+// spea2_select.hip: SPEA2's fitness in two launches (n ≤ evx_spea2_fitness_max_n(), m ≤ evx_spea2_max_m(): S, nd, msk = nd without NaN rows,
+// D, R, sig = D + R and the nearest neighbour (nn_d2, nn_idx) of every row of msk among the others), the neighbour pass alone for a given mask,
+// and the truncation on one workgroup (objT the (M, n) transpose zero padded to M = evx_spea2_padded_m(m) rows, n ≤ evx_spea2_max_n();
+// keep (n,) the masked rows that stay, order (n_order,) the removed rows then −1, stats = {rescans, removed})
+int evx_spea2_max_n();
+int evx_spea2_fitness_max_n();
+int evx_spea2_max_m();
+int evx_spea2_padded_m(int m);
+void evx_spea2_fitness(const float* obj, int n, int m, int32_t* S, uint8_t* nd, uint8_t* msk, float* D, float* R, float* sig,
+                       float* nn_d2, int32_t* nn_idx, hipStream_t s);
+void evx_spea2_neighbours(const float* obj, int n, int m, const uint8_t* mask, float* nn_d2, int32_t* nn_idx, hipStream_t s);
+void evx_spea2_truncate(const float* objT, int n, int M, const uint8_t* mask, const float* nn_d2, const int32_t* nn_idx, int n_keep,
+                        uint8_t* keep, int64_t* order, int n_order, int32_t* stats, hipStream_t s);
 // sorted-block refinement of a warm-started eigendecomposition (eigh_sbr.hip, evoxmi/ops/sbr.py)
 int evx_sbr_nblocks(int n, int off);
 int evx_sbr_stat_parts();
