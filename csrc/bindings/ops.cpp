@@ -361,6 +361,19 @@ void sbr16_block_out(const at::Tensor& A, int64_t shift, int64_t sweeps, int64_t
                   dq.data_ptr<float>(), (int)sb, cur_stream(), skip.data_ptr<int>(), (float)skip_tol);
 }
 
+// the block solves of a slot whose perm the fused control + rank launch (sbr_dev_ctrl_rank) wrote
+void sbr16_block_only_out(const at::Tensor& A, int64_t shift, int64_t sweeps, int64_t sb, const at::Tensor& perm, at::Tensor& Q,
+                          at::Tensor& dq, const at::Tensor& skip, double skip_tol) {
+  CHECK_DEV(A); CHECK_F32(A);
+  const int64_t n = A.size(0);
+  TORCH_CHECK(A.dim() == 2 && A.size(1) == n && A.stride(1) == 1 && n <= evx_sbr16_max_n(), "sbr16_block_only_out: A n×n");
+  TORCH_CHECK(sb == 16 || sb == 32, "sbr16_block_only_out: sb");
+  TORCH_CHECK(perm.numel() >= n && perm.scalar_type() == at::kInt && Q.numel() >= evx_sbr16_nblocks((int)n, (int)sb) * sb * sb &&
+                  dq.numel() >= n && skip.scalar_type() == at::kInt, "sbr16_block_only_out: buffers");
+  evx_sbr16_block_only(A.data_ptr<float>(), (int)n, A.stride(0), (int)shift, (int)sweeps, perm.data_ptr<int>(), Q.data_ptr<float>(),
+                       dq.data_ptr<float>(), (int)sb, cur_stream(), skip.data_ptr<int>(), (float)skip_tol);
+}
+
 void sbr16_far_bq_out(const at::Tensor& A, const at::Tensor& perm, const at::Tensor& Q, const at::Tensor& dq, const at::Tensor& stats,
                       double thr_fac, const at::Tensor& theta, at::Tensor& X, const at::Tensor& B, at::Tensor& Bq, int64_t sb,
                       const at::Tensor& skip_far, const at::Tensor& skip_bq, bool pre) {
@@ -468,6 +481,29 @@ void sbr_dev_ctrl(const at::Tensor& part, int64_t nparts, int64_t j, int64_t K, 
                    log.data_ptr<double>(), (int)(log.numel() / 4), log_count.data_ptr<int>(), cur_stream(), (int)prm[7],
                    prm.size() > 8 ? (int)prm[8] : 0, prm.size() > 9 ? (int)prm[9] : 0, prm.size() > 10 ? (int)prm[10] : 0,
                    prm.size() > 11 ? (int)prm[11] : -1, rs, rr, rl);
+}
+
+// control step after iteration j (−1 ≤ j < K − 1) + ranking of slot j + 1 in one launch (eigh_sbr_dev.hip)
+void sbr_dev_ctrl_rank(const at::Tensor& part, int64_t nparts, int64_t j, int64_t K, at::Tensor& hist, at::Tensor& alpha, at::Tensor& theta,
+                       at::Tensor& ctrl, at::Tensor& st, std::vector<double> prm, int64_t ns_iters, const at::Tensor& A,
+                       at::Tensor& w_init, int64_t shift, at::Tensor& perm) {
+  CHECK_DEV(A); CHECK_F32(A);
+  const int64_t n = A.size(0);
+  TORCH_CHECK(A.dim() == 2 && A.size(1) == n && A.stride(1) == 1 && n >= 1 && n <= evx_sbr16_max_n(), "sbr_dev_ctrl_rank: A n×n");
+  TORCH_CHECK(j >= -1 && j + 1 < K, "sbr_dev_ctrl_rank: the last control step runs on its own (sbr_dev_ctrl)");
+  TORCH_CHECK(shift >= 0 && shift < n, "sbr_dev_ctrl_rank: shift in [0, n)");
+  TORCH_CHECK(prm.size() >= 8, "sbr_dev_ctrl_rank: params as sbr_dev_ctrl");
+  TORCH_CHECK(part.scalar_type() == at::kDouble && hist.scalar_type() == at::kDouble && hist.numel() >= 4 * (K + 1) &&
+                  ctrl.scalar_type() == at::kInt && ctrl.numel() >= 8 * K && alpha.numel() >= K + 1 && theta.numel() >= K &&
+                  st.scalar_type() == at::kInt && st.numel() >= 8 && part.numel() >= 4 * nparts && w_init.numel() >= n &&
+                  perm.scalar_type() == at::kInt && perm.numel() >= n,
+              "sbr_dev_ctrl_rank: buffers");
+  float p6[7] = {(float)prm[0], (float)prm[1], (float)prm[2], (float)prm[3], (float)prm[4], (float)prm[5], (float)prm[6]};
+  evx_sbr_dev_ctrl_rank(part.data_ptr<double>(), (int)nparts, (int)j, (int)K, hist.data_ptr<double>(), alpha.data_ptr<float>(),
+                        theta.data_ptr<float>(), ctrl.data_ptr<int>(), st.data_ptr<int>(), p6, (int)ns_iters, A.data_ptr<float>(),
+                        A.stride(0), (int)n, w_init.data_ptr<float>(), (int)shift, perm.data_ptr<int>(), cur_stream(), (int)prm[7],
+                        prm.size() > 8 ? (int)prm[8] : 0, prm.size() > 9 ? (int)prm[9] : 0, prm.size() > 10 ? (int)prm[10] : 0,
+                        prm.size() > 11 ? (int)prm[11] : -1);
 }
 
 std::vector<at::Tensor> argsort_f32(const at::Tensor& keys, int64_t descending) {
@@ -1655,6 +1691,8 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("sbr_dev_prep(Tensor X, Tensor X2, Tensor X3, Tensor(c!) alpha, Tensor(a!) P, Tensor(b!) MT, Tensor ctrl, Tensor? work=None, float tau=1.0, Tensor? xpart=None, Tensor? copy_src=None, Tensor(d!)? copy_dst=None, int minus_id=0) -> ()");
   m.def("sbr_dev_copy(Tensor src, Tensor(a!) dst, Tensor skip) -> ()");
   m.def("sbr_dev_ctrl(Tensor part, int nparts, int j, int K, Tensor(a!) hist, Tensor(b!) alpha, Tensor(c!) theta, Tensor(d!) ctrl, Tensor(e!) st, float[] prm, int ns_iters, Tensor A, Tensor(f!) w_out, Tensor(g!) eig_stats, Tensor(h!) w_init, Tensor(i!) log, Tensor(j!) log_count, Tensor(k!)? rep_seq=None, Tensor(l!)? rep_ring=None) -> ()");
+  m.def("sbr16_block_only_out(Tensor A, int shift, int sweeps, int sb, Tensor perm, Tensor(b!) Q, Tensor(c!) dq, Tensor skip, float skip_tol=0.0) -> ()");
+  m.def("sbr_dev_ctrl_rank(Tensor part, int nparts, int j, int K, Tensor(a!) hist, Tensor(b!) alpha, Tensor(c!) theta, Tensor(d!) ctrl, Tensor(e!) st, float[] prm, int ns_iters, Tensor A, Tensor(f!) w_init, int shift, Tensor(g!) perm) -> ()");
   m.def("gemm_ks_set_tile(int t) -> ()");
   m.def("gemm_ks_set_prec(int prec) -> ()");
   m.def("gemm_ks_set_nw8(int tiles) -> ()");
@@ -1753,6 +1791,8 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("sbr_dev_prep", &sbr_dev_prep);
   m.impl("sbr_dev_copy", &sbr_dev_copy);
   m.impl("sbr_dev_ctrl", &sbr_dev_ctrl);
+  m.impl("sbr_dev_ctrl_rank", &sbr_dev_ctrl_rank);
+  m.impl("sbr16_block_only_out", &sbr16_block_only_out);
   m.impl("pso_update", &pso_update);
   m.impl("lsmop_g", &lsmop_g);
   m.impl("cma_delta_gemv", &cma_delta_gemv);

@@ -279,6 +279,8 @@ void evx_sbr_damping(const float* X2, int n, int64_t ldx, const float* V, float*
                      const int* skip = nullptr, int no_final = 0, const double* xpart = nullptr, int nparts = 0);
 void evx_sbr16_block(const float* A, int n, int64_t lda, int shift, int sweeps, int* perm, float* Q, float* dq, int sb, hipStream_t s,
                      const int* skip = nullptr, float skip_tol = 0.f);
+void evx_sbr16_block_only(const float* A, int n, int64_t lda, int shift, int sweeps, int* perm, float* Q, float* dq, int sb,
+                          hipStream_t s, const int* skip = nullptr, float skip_tol = 0.f);
 void evx_sbr16_far(const float* A, int n, int64_t lda, const int* perm, const float* Q, const float* dq, const double* stats,
                    float thr_fac, float theta, float* X, int64_t ldx, int sb, hipStream_t s,
                    const float* theta_ptr = nullptr, const int* skip = nullptr);
@@ -310,6 +312,10 @@ void evx_sbr_dev_copy(const float* src, float* dst, int64_t n, const int* skip, 
 void evx_sbr_dev_ctrl(const double* part, int nparts, int j, int K, double* hist, float* alpha, float* theta, int* ctrl, int* st,
                       const float* prm6, int ns_iters, const float* A, int64_t lda, int n, float* w_out, double* eig_stats, float* w_init,
                       double* log, int log_len, int* log_count, hipStream_t s, int lean_from = 1 << 30, int recover = 0, int lean_guard = 0, int xgate = 0, int damp_from = -1, int* rep_seq = nullptr, double* rep_ring = nullptr, int rep_len = 0);
+// the control step after iteration j and the ranking of slot j + 1 (shift, perm) in one launch; j + 1 < K
+void evx_sbr_dev_ctrl_rank(const double* part, int nparts, int j, int K, double* hist, float* alpha, float* theta, int* ctrl, int* st,
+                           const float* prm6, int ns_iters, const float* A, int64_t lda, int n, float* w_init, int shift, int* perm,
+                           hipStream_t s, int lean_from, int recover, int lean_guard, int xgate, int damp_from);
 // far generator + Bq in one launch (skip_far / skip_bq: their control words)
 void evx_sbr16_far_bq(const float* A, int n, int64_t lda, const int* perm, const float* Q, const float* dq, const double* stats,
                       float thr_fac, const float* theta_ptr, float* X, int64_t ldx, const float* B, int rows, int64_t ldb, float* Bq,

@@ -43,46 +43,15 @@ constexpr int TP = 80;
 constexpr int TC = 66;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int BQR = 32;  // rows of a Bq tile: twice the workgroups of 64-row tiles, better latency hiding
-constexpr int kRankMax = 8192;    // largest n of the rank kernel (32 KB of keys in LDS)
-
-__device__ __forceinline__ float sort_key(float v) { return isnan(v) ? INFINITY : v; }
+constexpr int kRankMax = kSbrRankMax;      // largest n of the rank kernel (evoxmi_sbr.h)
+constexpr int kRankWaves = kSbrRankWaves;
 
 // ------------------------------------------------------------------ 1. ranks → shifted perm
-// 64 indices per workgroup; its 16 waves each count over a sixteenth of the keys (16 waves:
-// the counting loop is 4× shorter than with 4, and the launch stays at ⌈n/64⌉ workgroups)
-constexpr int kRankWaves = 16;
+// (body in evoxmi_sbr.h: the device schedule's fused control + rank launch runs it too)
 __global__ void __launch_bounds__(64 * kRankWaves) sbr16_rank_kernel(const float* __restrict__ A, int n, int64_t lda, int shift,
                                                                      int* __restrict__ perm, const int* __restrict__ skip) {
   if (skip && *skip) return;
-  __shared__ __attribute__((aligned(16))) float key[kRankMax + 16];
-  __shared__ int part[kRankWaves][64];
-  const int np = (n + 15) & ~15;  // padded with +inf: never below a real key (NaN keys are +inf too, ties by index)
-  for (int i = threadIdx.x; i < np; i += blockDim.x) key[i] = i < n ? sort_key(A[(int64_t)i * lda + i]) : INFINITY;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + lane;
-  const float ki = i < n ? key[i] : 0.f;
-  // each wave counts over a sixteenth of the keys, 4 keys per LDS broadcast read (ds_read_b128)
-  const int q = ((np / kRankWaves) + 3) & ~3, j0 = min(np, w * q), j1 = min(np, j0 + q);
-  int cnt = 0;
-#pragma unroll 4
-  for (int j = j0; j < j1; j += 4) {
-    const float4 k4 = *(const float4*)(key + j);  // same address across the wave: broadcast
-    cnt += (k4.x < ki) | ((k4.x == ki) & (j < i));
-    cnt += (k4.y < ki) | ((k4.y == ki) & (j + 1 < i));
-    cnt += (k4.z < ki) | ((k4.z == ki) & (j + 2 < i));
-    cnt += (k4.w < ki) | ((k4.w == ki) & (j + 3 < i));
-  }
-  part[w][lane] = cnt;
-  __syncthreads();
-  if (w == 0 && i < n) {
-    int r = 0;
-#pragma unroll
-    for (int v = 0; v < kRankWaves; ++v) r += part[v][lane];
-    int pos = r - shift;
-    if (pos < 0) pos += n;
-    perm[pos] = i;
-  }
+  evx_sbr16_rank_body(A, n, lda, shift, perm, blockIdx.x);
 }
 
 // circle-method round robin on SB slots: round r pairs (SB−1, r) and ((r+i) mod (SB−1), (r−i) mod (SB−1))
@@ -554,13 +523,19 @@ __global__ void __launch_bounds__(256) sbr_taylor4_prep_kernel(const float* __re
 int evx_sbr16_nblocks(int n, int sb) { return (n + sb - 1) / sb; }
 int evx_sbr16_max_n() { return kRankMax; }
 
-void evx_sbr16_block(const float* A, int n, int64_t lda, int shift, int sweeps, int* perm, float* Q, float* dq, int sb, hipStream_t s,
-                     const int* skip, float skip_tol) {
-  sbr16_rank_kernel<<<(n + 63) / 64, 64 * kRankWaves, 0, s>>>(A, n, lda, shift, perm, skip);
+// the block solves alone, on a perm some earlier launch ranked (the device schedule's fused control + rank launch)
+void evx_sbr16_block_only(const float* A, int n, int64_t lda, int shift, int sweeps, int* perm, float* Q, float* dq, int sb, hipStream_t s,
+                          const int* skip, float skip_tol) {
   if (sb == 32)
     sbr16_block_kernel<32><<<(n + 31) / 32, 512, 0, s>>>(A, n, lda, perm, sweeps, Q, dq, skip, shift, skip_tol);
   else
     sbr16_block_kernel<16><<<(n + 15) / 16, 128, 0, s>>>(A, n, lda, perm, sweeps, Q, dq, skip, shift, skip_tol);
+}
+
+void evx_sbr16_block(const float* A, int n, int64_t lda, int shift, int sweeps, int* perm, float* Q, float* dq, int sb, hipStream_t s,
+                     const int* skip, float skip_tol) {
+  sbr16_rank_kernel<<<(n + 63) / 64, 64 * kRankWaves, 0, s>>>(A, n, lda, shift, perm, skip);
+  evx_sbr16_block_only(A, n, lda, shift, sweeps, perm, Q, dq, sb, s, skip, skip_tol);
 }
 
 void evx_sbr16_far(const float* A, int n, int64_t lda, const int* perm, const float* Q, const float* dq, const double* stats,

@@ -39,27 +39,6 @@
 
 namespace {
 
-// control words per refinement slot (documented above)
-constexpr int kCW = 8;
-
-struct SbrDevParams {
-  float tol, ns_kappa, damp_kappa, t4_kappa, near_only;
-  float theta0;  // local far threshold factor once κ ≤ theta_kappa (0: only after a stall)
-  float theta_kappa;
-  int ns_iters;
-  int lean_from;  // slots ≥ lean_from carry no damping / Newton–Schulz / X³ kernels (order 4, undamped)
-  int recover;    // divergences recovered by a forced damped step before the solve gives up (0: stop at the first)
-  int lean_guard; // 1: a lean slot whose step would need damping / Newton–Schulz / order 6 stops the solve (capped)
-  int xgate;      // 1: the damping kernels are scheduled for every full-slot far step and gate themselves (sbr_dev_prep)
-  int damp_from;  // slots ≥ damp_from carry no damping kernels (≤ lean_from; the late schedule keeps them in slot 0 only)
-};
-
-__device__ __forceinline__ void rel_kappa(const double* h, double& r, double& k) {
-  const double off = fmax(h[0], 0.0), dg = h[1], mn = h[2], mx = h[3];
-  r = dg > 0.0 ? sqrt(off / dg) : (double)NAN;
-  k = mx > mn ? sqrt(off) / (mx - mn) : (double)INFINITY;
-}
-
 // Taylor operands of exp(αX) for the order the control word selects (sel6), with M of
 // exp(−αX) (the transposed product, ops/sbr.py:expm_t_device).  V2 != null: when this
 // iteration's damping ran (ctrl[2] == 0) every workgroup forms α from its power-step vectors
@@ -183,7 +162,7 @@ __global__ void __launch_bounds__(256) sbr_dev_copy_kernel(const float* __restri
   for (int64_t e = 4 * n4 + g; e < n; e += stride) dst[e] = src[e];
 }
 
-// j = −1: the initial Bᵀ C B; j ≥ 0: after iteration j.  One workgroup.
+// j = −1: the initial Bᵀ C B; j ≥ 0: after iteration j.  One workgroup (body in evoxmi_sbr.h).
 __global__ void __launch_bounds__(256) sbr_dev_ctrl_kernel(const double* __restrict__ part, int nparts, int j, int K,
                                                            double* __restrict__ hist, float* __restrict__ alpha,
                                                            float* __restrict__ theta, int* __restrict__ ctrl, int* __restrict__ st,
@@ -192,191 +171,32 @@ __global__ void __launch_bounds__(256) sbr_dev_ctrl_kernel(const double* __restr
                                                            float* __restrict__ w_init, double* __restrict__ log, int log_len,
                                                            int* __restrict__ log_count, int* __restrict__ rep_seq, double* rep_ring,
                                                            int rep_len) {
-  __shared__ double s[4][4];
-  __shared__ int s_keep;
-  const int t = threadIdx.x;
-  const bool executed = j < 0 || ctrl[kCW * j] == 0;
-  double* hj1 = hist + 4 * (j + 1);
-  if (executed) {
-    double off = 0.0, dg = 0.0, mn = DBL_MAX, mx = -DBL_MAX;
-    for (int i = t; i < nparts; i += 256) {
-      off += part[4 * i];
-      dg += part[4 * i + 1];
-      mn = fmin(mn, part[4 * i + 2]);
-      mx = fmax(mx, part[4 * i + 3]);
-    }
-    // wave reductions (no barrier), then the four wave results through LDS: one barrier
-    // instead of the eight of a 256-wide tree (this kernel sits on the schedule's serial path)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      off += __shfl_xor(off, o);
-      dg += __shfl_xor(dg, o);
-      mn = fmin(mn, __shfl_xor(mn, o));
-      mx = fmax(mx, __shfl_xor(mx, o));
-    }
-    if ((t & 63) == 0) {
-      s[0][t >> 6] = off;
-      s[1][t >> 6] = dg;
-      s[2][t >> 6] = mn;
-      s[3][t >> 6] = mx;
-    }
-    __syncthreads();
-    if (t == 0) {
-      hj1[0] = (s[0][0] + s[0][1]) + (s[0][2] + s[0][3]);
-      hj1[1] = (s[1][0] + s[1][1]) + (s[1][2] + s[1][3]);
-      hj1[2] = fmin(fmin(s[2][0], s[2][1]), fmin(s[2][2], s[2][3]));
-      hj1[3] = fmax(fmax(s[3][0], s[3][1]), fmax(s[3][2], s[3][3]));
-    }
-  } else if (t < 4) {
-    hj1[t] = hist[4 * j + t];
-  }
-  if (j < 0) {  // the warm-start diagonal: the result if the refinement has to be abandoned
-    for (int i = t; i < n; i += 256) w_init[i] = A[(int64_t)i * lda + i];
-  }
-  __syncthreads();
-  if (t == 0) {
-    if (j < 0) {
-      st[0] = 0;  // stopped
-      st[1] = 0;  // fallback
-      st[2] = 0;  // iterations run
-      st[3] = 1;  // last_far
-      st[4] = 0;  // theta sticky
-      st[6] = 0;  // converged
-      st[7] = 0;  // status bits | recoveries << 8
-      alpha[0] = 1.f;
-    }
-    double r, k;
-    rel_kappa(hj1, r, k);
-    double r0, k0;
-    rel_kappa(hist, r0, k0);  // the warm start's off-norm
-    // orthogonality monitor for free: ‖BᵀCB‖_F = ‖C‖_F for an orthogonal B, so the Frobenius
-    // norm of A (off + diag parts, both in the stats) drifting from the warm start's means the
-    // basis lost orthogonality — which the relative off-norm alone does not see
-    const double F0 = hist[0] + hist[1], F = hj1[0] + hj1[1];
-    const bool ortho = F0 > 0.0 && fabs(F / F0 - 1.0) <= 1e-3;
-    bool force = false;       // the next iteration must be damped + re-orthonormalised
-    // the solve stops here keeping the better basis: the current one (finite, orthogonal and
-    // closer to diagonal), or the warm start
-    auto give_up = [&](bool finite_now) {
-      st[0] = 1;
-      st[1] = (finite_now && ortho && r < r0) ? 0 : 1;
-    };
-    if (j >= 0 && executed && !st[0]) {
-      st[2] = j + 1;
-      double rp, kp;
-      rel_kappa(hist + 4 * j, rp, kp);
-      const bool far_j = ctrl[kCW * j + 1] == 0;
-      if (!ortho) st[7] |= 4;
-      if (!isfinite(r)) {
-        give_up(false);  // the basis itself is broken: back to the warm start
-      } else if (r > 1.5 * rp || !ortho) {
-        if ((st[7] >> 8) < prm.recover) {
-          st[7] = (st[7] | 1) + (1 << 8);
-          force = true;
-          st[3] = far_j ? 1 : 0;
-        } else {
-          give_up(true);
-        }
-      } else {
-        // an undamped far iteration close to the tolerance that barely helped: pairs in a
-        // cluster denser than the global threshold assumes — local threshold from now on
-        if (far_j && alpha[j + 1] >= 1.f && r < 100.0 * prm.tol && r > 0.6 * rp) st[4] = 1;
-        st[3] = far_j ? 1 : 0;
-      }
-    }
-    if (!st[0] && r <= prm.tol && ortho) {
-      st[0] = 1;
-      st[6] = 1;
-    }
-    const int nx = j + 1;
-    if (nx < K) {
-      int* c = ctrl + kCW * nx;
-      const bool lean = nx >= prm.lean_from;
-      const bool nodamp = nx >= prm.damp_from;  // no damping kernels in this slot (lean slots have none either)
-      if (!st[0]) {
-        // step size of the iteration just run (1 at the start); a lean slot's step is bounded
-        // to a negligible Taylor remainder (sbr_dev_prep), so its α < 1 asks for no Newton–Schulz
-        const float a_prev = (nx - 1 >= prm.lean_from) ? 1.f : alpha[nx];
-        // after a divergence every further far step is damped and re-orthonormalised (sticky):
-        // in the clustered spectra that diverge, an undamped step right after the recovery
-        // diverges again (profiles/r5_eigh_recover.txt)
-        const bool sticky = (st[7] & 1) != 0;
-        const bool ns = force || sticky || nx < prm.ns_iters || a_prev < 1.f || k > prm.ns_kappa;
-        const bool damp = force || sticky || nx == 0 || k > prm.damp_kappa;
+  evx_sbr_dev_ctrl_body(part, nparts, j, K, hist, alpha, theta, ctrl, st, prm, A, lda, n, w_out, eig_stats, w_init, log, log_len,
+                        log_count, rep_seq, rep_ring, rep_len);
+}
 
-        const bool far = force || !(nx > 0 && r <= prm.near_only * prm.tol && st[3]);
-        const bool six = !(k < prm.t4_kappa);
-        // (a lean slot still takes an order-4 step where the rules would pick order 6: the
-        // truncation is O(‖X‖⁵/120) and stays orthogonal to that order; damping and
-        // Newton–Schulz are the safety steps it cannot skip)
-        if (far && prm.lean_guard && ((lean && (ns || damp)) || (nodamp && damp))) {
-          // the lean slot has no damping / Newton–Schulz / order-6 kernels: taking its plain
-          // order-4 step here is unguarded — stop, capped (the host escalates the schedule)
-          st[7] |= 2;
-          give_up(true);
-        } else {
-          c[0] = 0;
-          c[1] = far ? 0 : 1;
-          // 0: damp (κ rule), 2: the generator's free bounds decide (xgate), 1: no damping
-          c[2] = (far && !lean && !nodamp) ? (damp ? 0 : (prm.xgate ? 2 : 1)) : 1;
-          c[3] = (far && six && !lean) ? 0 : 1;
-          c[4] = (six && !lean) ? 1 : 0;
-          c[5] = (far && ns && !lean) ? 0 : 1;
-          c[6] = (ns && !lean) ? 1 : 0;
-          c[7] = far ? 1 : 0;
-          // local far threshold: sticky after a stalled far iteration, or (theta0) once the far
-          // step is small (κ ≤ theta_kappa: with larger steps the extra strongly coupled far pairs
-          // rotated at once can make a cold-start iteration diverge)
-          const bool th = st[4] || (prm.theta0 > 0.f && k <= prm.theta_kappa);
-          theta[nx] = th ? (prm.theta0 > 0.f ? prm.theta0 : 1.f) : 0.f;
-          alpha[nx + 1] = 1.f;  // the damping kernel of iteration nx overwrites it when it runs
-        }
-      }
-      if (st[0]) {
-        c[0] = 1; c[1] = 1; c[2] = 1; c[3] = 1; c[4] = 0; c[5] = 1; c[6] = 0; c[7] = 1;
-      }
-    }
-    if (nx == K) {
-      const bool fb = st[1] != 0;
-      double rf, kf;
-      rel_kappa(fb ? hist : hist + 4 * K, rf, kf);
-      eig_stats[0] = rf;
-      const bool conv = st[6] != 0 && rf <= prm.tol;
-      eig_stats[1] = (double)((conv ? 0 : 1) | ((st[7] & 1) ? 2 : 0) | ((st[7] & 2) ? 4 : 0) | ((st[7] & 4) ? 8 : 0));
-      eig_stats[2] = (double)st[2];
-      eig_stats[3] = fb ? 1.0 : 0.0;
-      // keep: the restore copy (warm-start basis → output) is skipped unless the refinement
-      // diverged or no iteration ran at all (the solve then never wrote its output basis: the
-      // warm start is read directly by the first BᵀCB and the first iteration, no copy launch)
-      st[5] = (fb || st[2] == 0) ? 0 : 1;
-      if (log && log_len > 0) {  // per-solve history ring (read by benches after the timed loop)
-        const int c = *log_count;
-        double* o = log + 4 * (int64_t)(c % log_len);
-        o[0] = eig_stats[0];
-        o[1] = eig_stats[1];
-        o[2] = eig_stats[2];
-        o[3] = eig_stats[3];
-        *log_count = c + 1;
-      }
-      if (rep_seq) {  // the solve's health into the host-mapped ring (CMAES schedule; was sbr_report_kernel)
-        const int q = *rep_seq;
-        double* o = rep_ring + 5 * (int64_t)(q % rep_len);
-        o[0] = eig_stats[0];
-        o[1] = eig_stats[1];
-        o[2] = eig_stats[2];
-        o[3] = eig_stats[3];
-        o[4] = (double)q;
-        __threadfence_system();
-        *rep_seq = q + 1;
-      }
-    }
-    s_keep = st[1] ? 0 : 1;
+// The control step after iteration j (j + 1 < K) and the ranking of slot j + 1 in ONE launch:
+// the rank kernel followed the control kernel directly and took nothing from it but its skip
+// word.  Workgroups 1 … ⌈n/64⌉ rank, unconditionally — diag(A) is final (the previous launch
+// wrote it) and perm is read only by slot j + 1's block and far / Bq kernels, which still test
+// their skip words — and workgroup 0 runs the control step beside them, in place on the same
+// buffers.  No workgroup reads what another writes: no inter-workgroup communication.
+// (Workgroup 0 running the control step AND a ranking tile made the launch as long as the two
+// kernels it replaced — 1.3108 vs 1.3173 ms per flagship generation, profiles/NOTES.md — because
+// both are latency chains; a workgroup of its own puts the two chains side by side.)
+__global__ void __launch_bounds__(64 * kSbrRankWaves) sbr_dev_ctrl_rank_kernel(const double* __restrict__ part, int nparts, int j,
+                                                                               int K, double* __restrict__ hist,
+                                                                               float* __restrict__ alpha, float* __restrict__ theta,
+                                                                               int* __restrict__ ctrl, int* __restrict__ st,
+                                                                               SbrDevParams prm, const float* __restrict__ A,
+                                                                               int64_t lda, int n, float* __restrict__ w_init, int shift,
+                                                                               int* __restrict__ perm) {
+  if (blockIdx.x == 0) {
+    evx_sbr_dev_ctrl_body(part, nparts, j, K, hist, alpha, theta, ctrl, st, prm, A, lda, n, nullptr, nullptr, w_init, nullptr, 0, nullptr,
+                          nullptr, nullptr, 0);
+    return;
   }
-  __syncthreads();
-  if (j + 1 == K) {
-    const bool keep = s_keep != 0;
-    for (int i = t; i < n; i += 256) w_out[i] = keep ? A[(int64_t)i * lda + i] : w_init[i];
-  }
+  evx_sbr16_rank_body(A, n, lda, shift, perm, blockIdx.x - 1);
 }
 
 }  // namespace
@@ -408,4 +228,13 @@ void evx_sbr_dev_ctrl(const double* part, int nparts, int j, int K, double* hist
                  damp_from < 0 ? lean_from : min(damp_from, lean_from)};
   sbr_dev_ctrl_kernel<<<1, 256, 0, s>>>(part, nparts, j, K, hist, alpha, theta, ctrl, st, p, A, lda, n, w_out, eig_stats, w_init, log,
                                         log_len, log_count, j + 1 == K ? rep_seq : nullptr, rep_ring, rep_len);
+}
+
+void evx_sbr_dev_ctrl_rank(const double* part, int nparts, int j, int K, double* hist, float* alpha, float* theta, int* ctrl, int* st,
+                           const float* prm6, int ns_iters, const float* A, int64_t lda, int n, float* w_init, int shift, int* perm,
+                           hipStream_t s, int lean_from, int recover, int lean_guard, int xgate, int damp_from) {
+  SbrDevParams p{prm6[0], prm6[1], prm6[2], prm6[3], prm6[4], prm6[5], prm6[6], ns_iters, lean_from, recover, lean_guard, xgate,
+                 damp_from < 0 ? lean_from : min(damp_from, lean_from)};
+  sbr_dev_ctrl_rank_kernel<<<1 + (n + 63) / 64, 64 * kSbrRankWaves, 0, s>>>(part, nparts, j, K, hist, alpha, theta, ctrl, st, p, A, lda, n,
+                                                                        w_init, shift, perm);
 }

@@ -19,7 +19,9 @@ generation.  The reference decomposes C inside its one jitted step
   control words with :func:`evoxmi.ops.sbr.decide`'s rules (tolerance stop, Newton–Schulz
   while κ is large or after a damped step, damping at iteration 0 / large κ, near-only
   close to the tolerance, Taylor order 4 once κ is small, the sticky local threshold, and
-  the divergence stop — which restores the warm-start basis).
+  the divergence stop — which restores the warm-start basis).  The control step of slot j
+  runs inside slot j + 1's rank launch (its own workgroup, ``sbr_dev_ctrl_rank``); only the
+  last one is a launch of its own.
 
 No host read, no iteration plan, no state outside the algorithm's ``State``: a solve
 depends only on (C, B_prev), so a checkpoint-resumed run is bitwise identical
@@ -128,10 +130,14 @@ class DeviceSBR:
     """Persistent buffers + the fixed iteration schedule for one (n, device, config)."""
 
     def __init__(self, n: int, device, cfg: SBRConfig, iters: int, lean_from: int = None, xgate: bool = None,
-                 damp_from: int = None, basis_x3: bool = False):
+                 damp_from: int = None, basis_x3: bool = False, fold: bool = True):
         if cfg.block not in (16, 32):
             raise ValueError("the device schedule uses the shifted-layout blocks (16 / 32)")
         self.n, self.cfg, self.K = n, cfg, int(iters)
+        # fold: the control step after slot j runs inside slot j + 1's rank launch (one launch per
+        # slot fewer); False keeps the separate control / rank launches (bit-identical results:
+        # tests/test_sbr_fold_gpu.py, and the A/B of profiles/NOTES.md)
+        self.fold = bool(fold)
         # slots ≥ lean_from launch no damping / Newton–Schulz / X³ kernels (their variants are
         # only chosen in the first iterations of a warm-started solve): a skipped lean slot
         # costs 7 launch boundaries fewer
@@ -215,16 +221,29 @@ class DeviceSBR:
         _ext.ops().sbr_dev_ctrl(self.part, self.nparts, j, self.K, self.hist, self.alpha, self.theta, self.ctrl, self.st, self.prm,
                                 int(self.cfg.ns_iters), self.A, self.w, self.eig_stats, self.w_init, log, self.log_count, seq, ring)
 
+    def _ctrl_rank(self, j, shift):
+        """Control step after slot ``j`` (−1: after the initial Bᵀ C B) and the ranking of slot j + 1, one launch."""
+        _ext.ops().sbr_dev_ctrl_rank(self.part, self.nparts, j, self.K, self.hist, self.alpha, self.theta, self.ctrl, self.st, self.prm,
+                                     int(self.cfg.ns_iters), self.A, self.w_init, shift, self.perm)
+
     def _iteration(self, j, C, B_in=None, report=None):
         ops = _ext.ops()
         cfg = self.cfg
         sb = cfg.block
         c = self.ctrl[CW * j : CW * j + CW]
         sk_all, sk_far, sk_damp, sk_x3, sel6, sk_ns, sel_ns, sk_copy = (c[i : i + 1] for i in range(8))
-        shift = (j % 2) * (sb // 2)
+        # (mod n: with n ≤ sb/2 the half-block shift is no position of the sorted order — the rank kernels take
+        # shift in [0, n), and an unreduced one sent their perm writes in front of the buffer)
+        shift = ((j % 2) * (sb // 2)) % self.n
         full = j < self.lean_from
         damp_slot = j < self.damp_from
-        ops.sbr16_block_out(self.A, shift, int(cfg.block_sweeps), sb, self.perm, self.Q, self.dq, sk_all, 0.0)
+        if self.fold:
+            # the previous slot's control step (it writes this slot's control words) and this slot's
+            # ranking in one launch; the ranking runs whether or not the slot is skipped
+            self._ctrl_rank(j - 1, shift)
+            ops.sbr16_block_only_out(self.A, shift, int(cfg.block_sweeps), sb, self.perm, self.Q, self.dq, sk_all, 0.0)
+        else:
+            ops.sbr16_block_out(self.A, shift, int(cfg.block_sweeps), sb, self.perm, self.Q, self.dq, sk_all, 0.0)
         # far generator X and Bq = B[:, perm]·blockdiag(Q) in one launch
         # (iteration 0 reads the warm-start basis itself: no copy of it into the workspace)
         ops.sbr16_far_bq_out(self.A, self.perm, self.Q, self.dq, self.hist[4 * j : 4 * j + 4], float(cfg.thr_fac),
@@ -265,7 +284,9 @@ class DeviceSBR:
                 mm(self.T, self.T, ta=True, mode=1, out=self.G, skip=sk_ns)
                 mm(self.T, self.G, tb=True, alpha=-0.5, beta=1.5, Cin=self.T, out=self.B, skip=sk_ns)
         self._btcb(C, sk_all)
-        self._ctrl(j, C, report)
+        if not self.fold or j == self.K - 1:
+            # the last slot's control step stays a launch of its own: the log, the report ring, w_out, the keep word
+            self._ctrl(j, C, report)
 
     # ------------------------------------------------------------------ solve
     def solve(self, C: torch.Tensor, B_prev: torch.Tensor, report=None, restore: bool = True):
@@ -278,7 +299,8 @@ class DeviceSBR:
         assert C.shape == (n, n) and B_prev.shape == (n, n)
         B_prev = B_prev if B_prev.is_contiguous() else B_prev.contiguous()
         self._btcb(C, self.never, B_prev)
-        self._ctrl(-1, C, report if self.K == 0 else None)
+        if not self.fold or self.K == 0:
+            self._ctrl(-1, C, report if self.K == 0 else None)
         for j in range(self.K):
             self._iteration(j, C, B_prev if j == 0 else None, report if j == self.K - 1 else None)
         # the refinement diverged, or no iteration ran (st[5] = 0): the warm-start basis is the result
