@@ -1582,6 +1582,92 @@ std::vector<at::Tensor> spea2_truncate(const at::Tensor& obj, const at::Tensor& 
   return {keep, order, stats};
 }
 
+// (M, n): the transpose zero padded to the kernels' compile-time objective counts
+at::Tensor bce_transposed(const at::Tensor& obj) {
+  const int64_t n = obj.size(0), m = obj.size(1), M = evx_bce_padded_m((int)m);
+  auto objT = at::zeros({M, n}, obj.options());
+  objT.narrow(0, 0, m).copy_(obj.t());
+  return objT;
+}
+
+void bce_check(const at::Tensor& obj, const char* who) {
+  CHECK_DEV(obj); CHECK_F32(obj); CHECK_CONTIG(obj);
+  TORCH_CHECK(obj.dim() == 2, who, ": obj float32 (n, m)");
+  TORCH_CHECK(obj.size(0) >= 1 && obj.size(0) <= evx_bce_max_n(), who, ": 1 <= n <= ", evx_bce_max_n());
+  TORCH_CHECK(obj.size(1) >= 1 && obj.size(1) <= evx_bce_max_m(), who, ": 1 <= m <= ", evx_bce_max_m());
+}
+
+// t, ws (the spans, then the radius), cnt of bce_select.hip's niche pass over the rows of mask (all rows without one)
+std::vector<at::Tensor> bce_niche(const at::Tensor& obj, const c10::optional<at::Tensor>& mask) {
+  bce_check(obj, "bce_niche");
+  const int64_t n = obj.size(0);
+  const uint8_t* mp = nullptr;
+  if (mask.has_value()) {
+    CHECK_DEV((*mask)); CHECK_CONTIG((*mask));
+    TORCH_CHECK(mask->scalar_type() == at::kBool && mask->dim() == 1 && mask->numel() == n && mask->device() == obj.device(),
+                "bce_niche: mask bool (n,) on obj's device");
+    mp = (const uint8_t*)mask->data_ptr<bool>();
+  }
+  c10::DeviceGuard g(obj.device());
+  const at::Tensor objT = bce_transposed(obj);
+  auto t = at::empty({n}, obj.options()), ws = at::empty({evx_bce_ws_floats()}, obj.options());
+  auto cnt = at::empty({}, obj.options().dtype(at::kLong));
+  evx_bce_niche(objT.data_ptr<float>(), (int)n, (int)objT.size(0), mp, t.data_ptr<float>(), ws.data_ptr<float>(), cnt.data_ptr<int64_t>(),
+                -1, cur_stream());
+  return {t, ws, cnt};
+}
+
+// keep, order, {rescans, removed}, n_nd, mask of bce_select.hip's PC selection; without a mask, the rows no row dominates
+std::vector<at::Tensor> bce_pc_select(const at::Tensor& obj, int64_t n_keep, const c10::optional<at::Tensor>& mask) {
+  bce_check(obj, "bce_pc_select");
+  const int64_t n = obj.size(0);
+  TORCH_CHECK(n_keep >= 1, "bce_pc_select: need n_keep >= 1");
+  c10::DeviceGuard g(obj.device());
+  const at::Tensor objT = bce_transposed(obj);
+  const int M = (int)objT.size(0);
+  at::Tensor msk;
+  if (mask.has_value()) {
+    msk = *mask;
+    CHECK_DEV(msk); CHECK_CONTIG(msk);
+    TORCH_CHECK(msk.scalar_type() == at::kBool && msk.dim() == 1 && msk.numel() == n && msk.device() == obj.device(),
+                "bce_pc_select: mask bool (n,) on obj's device");
+  } else {
+    msk = at::empty({n}, obj.options().dtype(at::kBool));
+    evx_bce_mask(objT.data_ptr<float>(), (int)n, M, (uint8_t*)msk.data_ptr<bool>(), cur_stream());
+  }
+  const int64_t n_order = std::max<int64_t>(n - n_keep, 0);
+  auto t = at::empty({n}, obj.options()), ws = at::empty({evx_bce_ws_floats()}, obj.options()), P = at::empty({n}, obj.options());
+  auto C = at::empty({n}, obj.options().dtype(at::kInt)), stats = at::empty({2}, obj.options().dtype(at::kInt));
+  auto n_nd = at::empty({}, obj.options().dtype(at::kLong));
+  auto keep = at::empty({n}, obj.options().dtype(at::kBool)), order = at::empty({n_order}, obj.options().dtype(at::kLong));
+  const uint8_t* mp = (const uint8_t*)msk.data_ptr<bool>();
+  evx_bce_niche(objT.data_ptr<float>(), (int)n, M, mp, t.data_ptr<float>(), ws.data_ptr<float>(), n_nd.data_ptr<int64_t>(), (int)n_keep,
+                cur_stream());
+  evx_bce_remove(objT.data_ptr<float>(), (int)n, M, mp, ws.data_ptr<float>(), n_nd.data_ptr<int64_t>(), P.data_ptr<float>(),
+                 C.data_ptr<int32_t>(), (int)n_keep,
+                 (uint8_t*)keep.data_ptr<bool>(), order.data_ptr<int64_t>(), (int)n_order, stats.data_ptr<int32_t>(), cur_stream());
+  return {keep, order, stats, n_nd, msk};
+}
+
+// whether at most one row of npc_obj lies within n_nd / N · (mean niche radius of pc_obj) of each row of pc_obj
+at::Tensor bce_explore(const at::Tensor& pc_obj, const at::Tensor& npc_obj, const at::Tensor& n_nd) {
+  bce_check(pc_obj, "bce_explore");
+  bce_check(npc_obj, "bce_explore");
+  CHECK_DEV(n_nd);
+  TORCH_CHECK(npc_obj.size(1) == pc_obj.size(1) && npc_obj.device() == pc_obj.device(), "bce_explore: one device, one objective count");
+  TORCH_CHECK(n_nd.scalar_type() == at::kLong && n_nd.numel() == 1 && n_nd.device() == pc_obj.device(), "bce_explore: n_nd one int64 word");
+  const int64_t N = pc_obj.size(0);
+  c10::DeviceGuard g(pc_obj.device());
+  const at::Tensor pcT = bce_transposed(pc_obj), npcT = bce_transposed(npc_obj);
+  auto t = at::empty({N}, pc_obj.options()), ws = at::empty({evx_bce_ws_floats()}, pc_obj.options());
+  auto cnt = at::empty({}, pc_obj.options().dtype(at::kLong)), out = at::empty({N}, pc_obj.options().dtype(at::kBool));
+  evx_bce_niche(pcT.data_ptr<float>(), (int)N, (int)pcT.size(0), nullptr, t.data_ptr<float>(), ws.data_ptr<float>(), cnt.data_ptr<int64_t>(),
+                -1, cur_stream());
+  evx_bce_count(pcT.data_ptr<float>(), (int)N, npcT.data_ptr<float>(), (int)npc_obj.size(0), (int)pcT.size(0), ws.data_ptr<float>(),
+                n_nd.data_ptr<int64_t>(), (uint8_t*)out.data_ptr<bool>(), cur_stream());
+  return out;
+}
+
 }  // namespace
 
 // OpenES gradient with Philox-regenerated noise: g[j] = Σ_i w[i] ε(row0 + i, j)
@@ -1715,6 +1801,9 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("ibea_truncate(Tensor obj_norm, Tensor f, Tensor C, float kappa, int n_remove, int n_keep) -> Tensor[]");
   m.def("spea2_fitness(Tensor obj) -> Tensor[]");
   m.def("spea2_truncate(Tensor obj, Tensor mask, int n_keep, Tensor? nn_d2, Tensor? nn_idx) -> Tensor[]");
+  m.def("bce_niche(Tensor obj, Tensor? mask) -> Tensor[]");
+  m.def("bce_pc_select(Tensor obj, int n_keep, Tensor? mask) -> Tensor[]");
+  m.def("bce_explore(Tensor pc_obj, Tensor npc_obj, Tensor n_nd) -> Tensor");
   m.def("moead_parents(Tensor nb, Tensor key, int row0=0, int rows=0) -> Tensor[]");
   m.def("moead_variation(Tensor pop, Tensor p0, Tensor p1, Tensor kx, Tensor km, Tensor lb, Tensor ub, float pro_c, float dis_c, float pro_m, float dis_m, int nm, int row0=0, int rows=0, Tensor? win=None, Tensor(a!)? out=None) -> Tensor");
   m.def("moead_halo_replace(Tensor(a!) obj, Tensor off_obj, Tensor W, Tensor z, Tensor zmax, Tensor rowptr, Tensor owner, Tensor slots, int func, Tensor(b!) win_h) -> ()");
@@ -1811,6 +1900,9 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("ibea_truncate", &ibea_truncate);
   m.impl("spea2_fitness", &spea2_fitness);
   m.impl("spea2_truncate", &spea2_truncate);
+  m.impl("bce_niche", &bce_niche);
+  m.impl("bce_pc_select", &bce_pc_select);
+  m.impl("bce_explore", &bce_explore);
   m.impl("moead_parents", &moead_parents);
   m.impl("moead_variation", &moead_variation);
   m.impl("moead_replace", &moead_replace);

@@ -260,6 +260,22 @@ void evx_spea2_fitness(const float* obj, int n, int m, int32_t* S, uint8_t* nd, 
 void evx_spea2_neighbours(const float* obj, int n, int m, const uint8_t* mask, float* nn_d2, int32_t* nn_idx, hipStream_t s);
 void evx_spea2_truncate(const float* objT, int n, int M, const uint8_t* mask, const float* nn_d2, const int32_t* nn_idx, int n_keep,
                         uint8_t* keep, int64_t* order, int n_order, int32_t* stats, hipStream_t s);
+// bce_select.hip: BCE-IBEA's PC selection and exploration (objT the (M, n) transpose zero padded to M = evx_bce_padded_m(m) rows;
+// ws evx_bce_ws_floats() floats: the spans and, last, the niche radius; cnt one word, the rows of the mask).  evx_bce_mask: the rows no
+// row dominates; evx_bce_niche: spans, t (n,) and the radius over the masked rows (mask == nullptr: all; with n_keep ≥ 0 t and the radius
+// are left unwritten where cnt ≤ n_keep, as are the scores: nothing will be removed); evx_bce_remove: the scores and
+// the one-workgroup removal (n ≤ evx_bce_max_n(); P, C (n,) work arrays; keep, order, stats as for SPEA2); evx_bce_count: out[i] = at
+// most one NPC row within n_nd / N · radius of PC row i
+int evx_bce_max_n();
+int evx_bce_max_m();
+int evx_bce_padded_m(int m);
+int evx_bce_ws_floats();
+void evx_bce_mask(const float* objT, int n, int M, uint8_t* mask, hipStream_t s);
+void evx_bce_niche(const float* objT, int n, int M, const uint8_t* mask, float* t, float* ws, int64_t* cnt, int n_keep, hipStream_t s);
+void evx_bce_remove(const float* objT, int n, int M, const uint8_t* mask, const float* ws, const int64_t* cnt, float* P, int32_t* C,
+                    int n_keep, uint8_t* keep, int64_t* order, int n_order, int32_t* stats, hipStream_t s);
+void evx_bce_count(const float* pcT, int N, const float* npcT, int Nn, int M, const float* ws, const int64_t* n_nd, uint8_t* out,
+                   hipStream_t s);
 // sorted-block refinement of a warm-started eigendecomposition (eigh_sbr.hip, evoxmi/ops/sbr.py)
 int evx_sbr_nblocks(int n, int off);
 int evx_sbr_stat_parts();

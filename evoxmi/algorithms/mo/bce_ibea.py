@@ -7,55 +7,31 @@ variation on NPC; NPC is always updated by IBEA environmental selection and PC b
 the PC selection over everything evaluated.  The reference mixes up the objective
 arrays between the two populations in its odd/even tells (e.g. ``fitness=npc_obj``
 in ``_tell_odd``); here each population keeps its own objectives.
+
+On a HIP device both selections and the exploration test are HIP kernels
+(``ops/ibea.py``, ``ops/bce.py``), ``n_nd`` and ``counter`` are device words and the
+odd branch has a fixed shape: ``ask`` and ``tell`` read nothing on the host, and
+``StdWorkflow(graph=True)`` captures a generation into a hipGraph, one graph per
+parity (``graph_variant``).  ``graph="auto"`` stays eager (``graph_auto``).
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
-from ...core import State
 from ...operators import crossover, selection
-from ...operators.selection.non_dominate import non_dominated_sort
+from ...ops import bce as bce_ops
 from ...ops import ibea as ibea_ops
 from ...ops import random as rnd
 from .common import MOAlgorithm
 
 
-def exploration(pc_obj, npc_obj, n_nd, n):
-    f_max, f_min = pc_obj.max(0).values, pc_obj.min(0).values
-    span = (f_max - f_min).clamp(min=1e-12)
-    npc_n = (npc_obj - f_min) / span
-    pc_n = (pc_obj - f_min) / span
-    d = torch.cdist(pc_n, pc_n).masked_fill(torch.eye(pc_n.shape[0], dtype=torch.bool, device=pc_obj.device), float("inf"))
-    d = torch.nan_to_num(d, nan=float("inf"))
-    sd = torch.sort(d, 1).values
-    r0 = sd[:, min(2, sd.shape[1] - 1)].mean()
-    r = n_nd / n * r0
-    return (torch.cdist(pc_n, npc_n) <= r).sum(1) <= 1
+exploration = bce_ops.exploration
 
 
 def pc_selection(pc, pc_obj, n):
-    rank = non_dominated_sort(pc_obj)
-    mask = rank == 0
-    n_nd = int(mask.sum())
-    if n_nd > n:
-        f = pc_obj[mask]
-        f_max, f_min = f.max(0).values, f.min(0).values
-        norm = (f - f_min) / (f_max - f_min).clamp(min=1e-12)
-        d = torch.cdist(norm, norm).masked_fill(torch.eye(n_nd, dtype=torch.bool, device=pc_obj.device), float("inf"))
-        sd = torch.sort(d, 1).values
-        r = sd[:, min(2, n_nd - 1)].sum() / n_nd
-        R = torch.clamp(d / r, max=1)
-        keep = torch.ones(n_nd, dtype=torch.bool, device=pc_obj.device)
-        for _ in range(n_nd - n):
-            score = torch.where(keep, 1 - torch.prod(R, 0), torch.full((n_nd,), -1.0, device=R.device))
-            i = int(torch.argmax(score))
-            keep[i] = False
-            R[i, :] = 1
-            R[:, i] = 1
-        idx = torch.nonzero(mask).flatten()[keep]
-    else:
-        idx = torch.nonzero(mask).flatten()
-        idx = torch.cat([idx, idx[:1].expand(n - idx.shape[0])])  # pad with the first member
+    idx, n_nd = bce_ops.pc_selection_indices(pc_obj, n)
     return pc[idx], pc_obj[idx], n_nd
 
 
@@ -65,43 +41,73 @@ def ibea_selection(pop, obj, n, kappa):
 
 
 class BCEIBEA(MOAlgorithm):
+    # graph="auto" keeps the eager generation it has always run for BCE-IBEA: test_bce_ibea_still_falls_back_to_eager
+    # (tests/test_ibea_select_gpu.py) asserts it.  The eager generation runs the same kernels and reads nothing on the
+    # host; graph=True captures.  Once that test asserts a capture instead, this line and Algorithm.graph_auto can go.
+    graph_auto = False
+
     def __init__(self, lb, ub, n_objs, pop_size, kappa=0.05, selection_op=None, mutation_op=None, crossover_op=None):
         super().__init__(lb, ub, n_objs, pop_size, mutation_op, crossover_op)
         self.kappa = kappa
         self.selection = selection.Tournament(n_round=pop_size)
         self.crossover_odd = crossover.SimulatedBinary(type=2)
+        self._parity = None  # of the generation being run, inside a graph_variant_context
 
     def setup(self, key):
         st = super().setup(key)
-        z = torch.zeros((self.pop_size, self.n_objs), device=st.population.device)
+        dev = st.population.device
+        z = torch.zeros((self.pop_size, self.n_objs), device=dev)
+        if dev.type == "cuda":  # device words: a captured generation updates them in place
+            return st.update(npc=st.population.clone(), npc_obj=z, n_nd=torch.zeros((), dtype=torch.int64, device=dev),
+                             counter=torch.ones((), dtype=torch.int64, device=dev))
         return st.update(npc=st.population.clone(), npc_obj=z, n_nd=0, counter=1)
 
+    # ---- the generation's parity is the workflow's: init_ask / init_tell are generation 0 and leave counter = 1,
+    # every tell adds one, so counter equals the workflow generation from generation 1 on
+    def graph_variant(self, generation: int):
+        return "explore" if generation % 2 else "ibea"
+
+    def graph_variant_set(self):
+        return ("explore", "ibea")
+
+    @contextlib.contextmanager
+    def graph_variant_context(self, variant):
+        prev, self._parity = self._parity, 1 if variant == "explore" else 0
+        try:
+            yield
+        finally:
+            self._parity = prev
+
+    def _pc_select(self, pop, obj):
+        idx, n_nd = bce_ops.pc_select(obj, self.pop_size)
+        return pop[idx], obj[idx], n_nd if obj.is_cuda else int(n_nd)
+
     def init_tell(self, state, fitness):
-        pc, pc_obj, n_nd = pc_selection(state.population, fitness, self.pop_size)
+        pc, pc_obj, n_nd = self._pc_select(state.population, fitness)
         return state.update(population=pc, fitness=pc_obj, npc=state.population, npc_obj=fitness, n_nd=n_nd)
 
     def ask(self, state):
         key, k1, x_key, mut_key = rnd.split(state.key, 4)
         N = self.pop_size
-        if state.counter % 2 == 0:  # IBEA variation on NPC
+        parity = self._parity if self._parity is not None else int(state.counter) % 2  # a direct call: one host read
+        if parity == 0:  # IBEA variation on NPC
             fit = -ibea_ops.fitness(state.npc_obj, self.kappa)[0]
             selected, _ = self.selection(k1, state.npc, fit)
             off = self.mutation(mut_key, self.crossover(x_key, selected))
-        else:  # PC exploration
-            s = exploration(state.fitness, state.npc_obj, state.n_nd, N)
-            if bool(s.any()):
-                cand = torch.nonzero(s).flatten()
-                mate = rnd.randint(k1, (N,), 0, N).to(cand.device)
-                first = cand[torch.arange(N, device=cand.device) % cand.shape[0]]
-                parents = torch.cat([state.population[first], state.population[mate]])
-                off = self.mutation(mut_key, self.crossover_odd(x_key, parents))
-            else:
-                off = state.population.clone()
+        else:  # PC exploration, fixed shape: the candidates first, cycled; no candidate keeps the population
+            s = bce_ops.explore(state.fitness, state.npc_obj, state.n_nd, N)
+            cnt = s.sum()
+            cand = torch.argsort((~s).to(torch.int8), stable=True)
+            mate = rnd.randint(k1, (N,), 0, N).to(cand.device)
+            first = cand[torch.arange(N, device=cand.device) % torch.clamp(cnt, min=1)]
+            parents = torch.cat([state.population[first], state.population[mate]])
+            varied = self.mutation(mut_key, self.crossover_odd(x_key, parents))
+            off = torch.where(cnt > 0, varied, state.population)
         off = torch.clamp(off, self.lb, self.ub)
         return off, state.update(next_generation=off, key=key)
 
     def tell(self, state, fitness):
         N = self.pop_size
         npc, npc_obj = ibea_selection(torch.cat([state.npc, state.next_generation]), torch.cat([state.npc_obj, fitness]), N, self.kappa)
-        pc, pc_obj, n_nd = pc_selection(torch.cat([state.population, state.next_generation]), torch.cat([state.fitness, fitness]), N)
+        pc, pc_obj, n_nd = self._pc_select(torch.cat([state.population, state.next_generation]), torch.cat([state.fitness, fitness]))
         return state.update(population=pc, fitness=pc_obj, npc=npc, npc_obj=npc_obj, n_nd=n_nd, counter=state.counter + 1)

@@ -29,6 +29,11 @@ class Algorithm(Stateful):
     def tell(self, state: State, fitness: torch.Tensor) -> State:
         return State()
 
+    # graph="auto" may capture this algorithm's generation; False keeps "auto" on the eager generation while an
+    # explicit graph=True still captures.  Only BCEIBEA sets it, for one test that pins its "auto" run as eager; the
+    # attribute and its branch in StdWorkflow.__init__ are to be removed together with that assertion.
+    graph_auto = True
+
     # ---- step variants: a host-known choice of how a generation runs (no device read)
     def graph_variant(self, generation: int) -> Optional[Hashable]:
         """Key of the step variant for workflow generation ``generation`` (``None``: the one

@@ -96,7 +96,8 @@ class StdWorkflow(Workflow):
             self.num_objectives = 1
         assert nan_policy in ("keep", "inf"), "nan_policy must be 'keep' or 'inf'"
         self.nan_policy = nan_policy
-        self.graph = graph
+        # graph="auto" leaves an algorithm that opts out (Algorithm.graph_auto) on its eager generation
+        self.graph = False if graph == "auto" and not getattr(algorithm, "graph_auto", True) else graph
         # optional evoxmi.utils.profiling.PhaseTimer (per-phase hipEvent timing, eager steps;
         # in graph mode the whole replay is one "graph_replay" phase)
         self.phase_timer = phase_timer
