@@ -1467,6 +1467,28 @@ at::Tensor nsga3_niche_select(const at::Tensor& rank, const at::Tensor& last_ran
   return idx;
 }
 
+// part (K·S,) region-major, counts (K,), worst (K,) of m2m_select.hip: every region's NSGA-II selection of S of its rows
+std::vector<at::Tensor> m2m_select(const at::Tensor& obj, const at::Tensor& region, const at::Tensor& rad, int64_t K, int64_t S) {
+  CHECK_DEV(obj); CHECK_F32(obj); CHECK_CONTIG(obj); CHECK_DEV(region); CHECK_CONTIG(region); CHECK_DEV(rad); CHECK_CONTIG(rad);
+  TORCH_CHECK(obj.dim() == 2, "m2m_select: obj float32 (n, m)");
+  const int64_t n = obj.size(0), m = obj.size(1);
+  TORCH_CHECK((region.scalar_type() == at::kInt || region.scalar_type() == at::kLong) && region.dim() == 1 && region.numel() == n,
+              "m2m_select: region int32 or int64 (n,)");
+  TORCH_CHECK(rad.scalar_type() == at::kLong && rad.dim() == 1 && rad.numel() == S, "m2m_select: rad int64 (S,)");
+  TORCH_CHECK(region.device() == obj.device() && rad.device() == obj.device(), "m2m_select: one device");
+  TORCH_CHECK(n >= 1 && n <= 8192, "m2m_select: 1 <= n <= 8192");
+  TORCH_CHECK(m >= 1 && m <= 16, "m2m_select: 1 <= m <= 16");
+  TORCH_CHECK(K >= 1 && K <= 1024, "m2m_select: 1 <= K <= 1024");
+  TORCH_CHECK(S >= 1 && S <= 8192, "m2m_select: 1 <= S <= 8192");
+  c10::DeviceGuard g(obj.device());
+  auto part = at::empty({K * S}, obj.options().dtype(at::kLong));
+  auto counts = at::empty({K}, obj.options().dtype(at::kInt));
+  auto worst = at::empty({K}, obj.options().dtype(at::kInt));
+  evx_m2m_select(obj.data_ptr<float>(), region.data_ptr(), region.scalar_type() == at::kLong ? 1 : 0, rad.data_ptr<int64_t>(), (int)n, (int)m,
+                 (int)K, (int)S, part.data_ptr<int64_t>(), counts.data_ptr<int>(), worst.data_ptr<int>(), cur_stream());
+  return {part, counts, worst};
+}
+
 at::Tensor sra_rank(const at::Tensor& I1, const at::Tensor& I2, const at::Tensor& u, const at::Tensor& pc) {
   CHECK_DEV(I1); CHECK_F32(I1); CHECK_CONTIG(I1); CHECK_DEV(I2); CHECK_F32(I2); CHECK_CONTIG(I2);
   CHECK_DEV(u); CHECK_F32(u); CHECK_CONTIG(u); CHECK_DEV(pc); CHECK_F32(pc);
@@ -1795,6 +1817,7 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("cma_eig_out(Tensor Bp, Tensor w, int d, Tensor? B_out=None, Tensor? B_alt=None, Tensor? keep=None) -> Tensor[]");
   m.def("nsga_select(Tensor rank, Tensor f, int N, int mask_pos) -> Tensor");
   m.def("nsga3_niche_select(Tensor rank, Tensor last_rank, Tensor group, Tensor group_dist, Tensor key, int N, int R) -> Tensor");
+  m.def("m2m_select(Tensor obj, Tensor region, Tensor rad, int K, int S) -> Tensor[]");
   m.def("sra_rank(Tensor I1, Tensor I2, Tensor u, Tensor pc) -> Tensor");
   m.def("sra_indicators(Tensor obj) -> Tensor[]");
   m.def("ibea_fitness(Tensor obj_norm, float kappa) -> Tensor[]");
@@ -1894,6 +1917,7 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("cma_eig_out", &cma_eig_out);
   m.impl("nsga_select", &nsga_select);
   m.impl("nsga3_niche_select", &nsga3_niche_select);
+  m.impl("m2m_select", &m2m_select);
   m.impl("sra_rank", &sra_rank);
   m.impl("sra_indicators", &sra_indicators);
   m.impl("ibea_fitness", &ibea_fitness);

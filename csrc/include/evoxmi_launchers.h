@@ -234,6 +234,10 @@ void evx_nsga_select(const int32_t* rank, const float* f, int n, int m, int N, i
 // nsga3_select.hip: NSGA-III niche-preserving selection (n ≤ 8192, R ≤ 8192), idx (N,) ascending rows
 void evx_nsga3_niche_select(const int32_t* rank, const int32_t* last_rank, const int64_t* group, const float* group_dist,
                             const int64_t* key, int n, int N, int R, int64_t* idx, hipStream_t s);
+// m2m_select.hip: MOEA/D-M2M's per-region NSGA-II selection, one workgroup per region (n ≤ 8192, m ≤ 16, K ≤ 1024);
+// region is (n,) int64 when region64 else int32, part (K·S,) region-major, counts and worst (K,)
+void evx_m2m_select(const float* f, const void* region, int region64, const int64_t* rad, int n, int m, int K, int S,
+                    int64_t* part, int32_t* counts, int32_t* worst, hipStream_t s);
 // sra_select.hip: SRA's stochastic ranking (n ≤ evx_sra_rank_max_n(), pc one device word, rank (n,) best first)
 // and its two indicators in one pass (m ≤ evx_sra_indicators_max_m())
 int evx_sra_rank_max_n();

@@ -22,46 +22,27 @@
 //   2. per objective, (cost, slot) over the front → crowding distance, neighbours
 //      exchanged through DPP shuffles + one LDS word per wave;
 //   3. (−cd, slot) → the remaining survivors.
-// Steps 2–3 sort 1024·IT keys with IT ∈ {1, 2, 4, 8} picked from the front size.
+// Steps 2–3 sort 1024·IT keys with IT ∈ {1, 2, 4, 8} picked from the front size.  They are
+// evx::crowd_select (evoxmi_crowd.h), shared with m2m_select.hip.
 // Float keys are canonicalised first (NaN → +qNaN, −0 → +0) so the bit-order radix sort
 // agrees with torch.sort (NaN last, ±0 equal, stable ties).
 // It replaces ~60 small library launches (sorts, gathers, scatters, lexsort) per
 // generation with one.
-#include <rocprim/block/block_radix_sort.hpp>
-
-#include "evoxmi_common.h"
+#include "evoxmi_crowd.h"
 
 namespace {
 
-constexpr int SEL_THREADS = 1024;
+constexpr int SEL_THREADS = evx::CROWD_THREADS;
 constexpr int SEL_ITEMS = 8;
 constexpr int SEL_MAXN = SEL_THREADS * SEL_ITEMS;  // 8192
 constexpr int SEL_WAVES = SEL_THREADS / 64;
 
 using rank_sort_t = rocprim::block_radix_sort<uint32_t, SEL_THREADS, SEL_ITEMS, uint32_t>;
-template <int IT>
-using key_sort_t = rocprim::block_radix_sort<float, SEL_THREADS, IT, uint32_t>;
 
 union SortStorage {
   typename rank_sort_t::storage_type r;
-  typename key_sort_t<1>::storage_type k1;
-  typename key_sort_t<2>::storage_type k2;
-  typename key_sort_t<4>::storage_type k4;
-  typename key_sort_t<8>::storage_type k8;
+  evx::CrowdSortStorage k;
 };
-
-template <int IT>
-__device__ __forceinline__ typename key_sort_t<IT>::storage_type& key_storage(SortStorage& st) {
-  if constexpr (IT == 1) return st.k1;
-  else if constexpr (IT == 2) return st.k2;
-  else if constexpr (IT == 4) return st.k4;
-  else return st.k8;
-}
-
-__device__ __forceinline__ float canon(float x) {
-  if (x != x) return __int_as_float(0x7fc00000);
-  return x == 0.f ? 0.f : x;
-}
 
 struct SelShared {
   SortStorage sort;
@@ -72,70 +53,6 @@ struct SelShared {
   float key0, keyl;
   int lo, hi, maxr;
 };
-
-// Crowding distance on the front slots [0, F) (rows srow[lo + slot]) and the `need`
-// best slots by (−cd, slot); IT items per thread cover F <= 1024·IT, so a small worst
-// front sorts IT·1024 keys instead of 8192.
-template <int IT>
-__device__ void crowd_select(SelShared& sh, const float* __restrict__ f, int m, int lo, int F, int need, int64_t* __restrict__ keep) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int base = t * IT;
-  using sort_t = key_sort_t<IT>;
-#pragma unroll
-  for (int i = 0; i < IT; ++i) sh.cd[base + i] = 0.f;
-  for (int obj = 0; obj < m; ++obj) {
-    float k[IT];
-    uint32_t v[IT];
-#pragma unroll
-    for (int i = 0; i < IT; ++i) {
-      const int s = base + i;
-      // +qNaN padding ties with real NaNs but sits after them (stable: larger slots)
-      k[i] = s < F ? canon(f[(int64_t)sh.srow[lo + s] * m + obj]) : __int_as_float(0x7fc00000);
-      v[i] = (uint32_t)s;
-    }
-    __syncthreads();  // sort storage reuse and the cd writes of the previous objective
-    sort_t().sort(k, v, key_storage<IT>(sh.sort));
-    // neighbour keys across the thread boundary: shuffles within the wave, LDS across waves
-    float prev = __shfl_up(k[IT - 1], 1);
-    float next = __shfl_down(k[0], 1);
-    if (lane == 0) sh.wave_first[wave] = k[0];
-    if (lane == 63) sh.wave_last[wave] = k[IT - 1];
-    if (t == 0) sh.key0 = k[0];
-#pragma unroll
-    for (int i = 0; i < IT; ++i)
-      if (base + i == F - 1) sh.keyl = k[i];
-    __syncthreads();
-    if (lane == 0 && wave > 0) prev = sh.wave_last[wave - 1];
-    if (lane == 63 && wave < SEL_WAVES - 1) next = sh.wave_first[wave + 1];
-    const float rng = sh.keyl - sh.key0;
-#pragma unroll
-    for (int i = 0; i < IT; ++i) {
-      const int p = base + i;
-      if (p < F) {
-        const float kp = i > 0 ? k[i - 1] : prev;
-        const float kn = i < IT - 1 ? k[i + 1] : next;
-        const float d = (p == 0 || p == F - 1) ? INFINITY : (kn - kp) / rng;
-        sh.cd[v[i]] += d;  // v is a permutation of the slots: no two threads share a slot
-      }
-    }
-  }
-  __syncthreads();
-  // remaining survivors: the worst front by (−cd, slot)
-  float k[IT];
-  uint32_t v[IT];
-#pragma unroll
-  for (int i = 0; i < IT; ++i) {
-    const int s = base + i;
-    k[i] = s < F ? canon(-sh.cd[s]) : __int_as_float(0x7fc00000);
-    v[i] = (uint32_t)s;
-  }
-  sort_t().sort(k, v, key_storage<IT>(sh.sort));
-#pragma unroll
-  for (int i = 0; i < IT; ++i) {
-    const int p = base + i;
-    if (p < need) keep[lo + p] = (int64_t)sh.srow[lo + v[i]];
-  }
-}
 
 __global__ void __launch_bounds__(SEL_THREADS) nsga_select_kernel(const int32_t* __restrict__ rank, const float* __restrict__ f, int n, int m,
                                                                    int N, int mask_pos, int64_t* __restrict__ keep) {
@@ -185,10 +102,10 @@ __global__ void __launch_bounds__(SEL_THREADS) nsga_select_kernel(const int32_t*
   for (int i = t; i < lo && i < N; i += SEL_THREADS) keep[i] = (int64_t)sh.srow[i];
   const int need = N - lo;
   if (need <= 0) return;  // uniform: every thread leaves together
-  if (F <= SEL_THREADS) crowd_select<1>(sh, f, m, lo, F, need, keep);
-  else if (F <= 2 * SEL_THREADS) crowd_select<2>(sh, f, m, lo, F, need, keep);
-  else if (F <= 4 * SEL_THREADS) crowd_select<4>(sh, f, m, lo, F, need, keep);
-  else crowd_select<8>(sh, f, m, lo, F, need, keep);
+  if (F <= SEL_THREADS) evx::crowd_select<1>(sh, sh.sort.k, f, m, lo, F, need, keep);
+  else if (F <= 2 * SEL_THREADS) evx::crowd_select<2>(sh, sh.sort.k, f, m, lo, F, need, keep);
+  else if (F <= 4 * SEL_THREADS) evx::crowd_select<4>(sh, sh.sort.k, f, m, lo, F, need, keep);
+  else evx::crowd_select<8>(sh, sh.sort.k, f, m, lo, F, need, keep);
 }
 
 }  // namespace

@@ -3,11 +3,18 @@
 The objective space is split into K sub-regions by K direction vectors; each keeps S
 members chosen by NSGA-II ranking among the solutions associated with it (padded
 with random solutions when fewer are available).  Variation is the M2M
-crossover/mutation whose spread shrinks with ``gen / max_gen``.  The per-region
-selection of the reference (a ``fori_loop`` over regions each running its own
-non-dominated sort) is done for all regions at once: the sort of region k only
-involves its own members, so one non-dominated sort of the merged set restricted
-by region gives identical ranks (dominance is evaluated within the region mask).
+crossover/mutation whose spread shrinks with ``gen / max_gen``.
+
+The association (the reference's ``fori_loop`` over regions, each running its own
+non-dominated sort) is ``associate``: the region of every row is the ``argmax`` of its
+cosine to the direction vectors, in torch; ``ops.m2m.select`` then picks every region's S
+rows.  On a HIP device that is one launch of ``m2m_select.hip``, one workgroup per region:
+it compacts the region's members, peels their fronts only until S members are ranked, and
+orders the cut front by crowding distance.  Nothing is read on the host, so a generation is
+capturable in a hipGraph.  On the CPU, and on a device above the kernel's caps (eager only),
+``association_indices`` does the same with one non-dominated sort of the merged set restricted
+by region (dominance is evaluated within the region mask, which gives the per-region ranks)
+and a host loop over the regions.
 """
 from __future__ import annotations
 
@@ -16,6 +23,7 @@ import torch
 from ...core import State
 from ...operators.sampling import UniformSampling
 from ...operators.selection.non_dominate import crowding_distance, lexsort
+from ...ops import m2m as m2m_ops
 from ...ops import random as rnd
 from ...utils.common import cos_dist, dominate_relation
 from .common import MOAlgorithm
@@ -56,13 +64,10 @@ def _rank_within(obj, region):
     return rank
 
 
-def associate(key, pop, obj, w, s):
-    k = w.shape[0]
-    n = pop.shape[0]
-    region = torch.argmax(cos_dist(obj, w), 1)
+def association_indices(obj, region, rad, k, s):
+    """The rows every region keeps, region-major (k·s,): the torch path and the oracle of ``ops.m2m.select``."""
     rank = _rank_within(obj, region).to(torch.float32)
     cols = []
-    rad = rnd.randint(key, (s,), 0, n).to(pop.device)
     for i in range(k):
         mask = region == i
         cnt = int(mask.sum())
@@ -75,7 +80,15 @@ def associate(key, pop, obj, w, s):
             worst = rk[order[s - 1]]
             cd = crowding_distance(obj, rk == worst)
             cols.append(lexsort([-cd, rk])[:s])
-    part = torch.stack(cols, 1).T.reshape(-1)  # region-major (Fortran flatten of (s, k))
+    return torch.stack(cols, 1).T.reshape(-1)  # region-major (Fortran flatten of (s, k))
+
+
+def associate(key, pop, obj, w, s):
+    k = w.shape[0]
+    n = pop.shape[0]
+    region = torch.argmax(cos_dist(obj, w), 1)
+    rad = rnd.randint(key, (s,), 0, n).to(pop.device)
+    part = m2m_ops.select(obj, region, rad, k, s)
     return pop[part], obj[part]
 
 
