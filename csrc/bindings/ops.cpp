@@ -1489,6 +1489,32 @@ std::vector<at::Tensor> m2m_select(const at::Tensor& obj, const at::Tensor& regi
   return {part, counts, worst};
 }
 
+// idx (N,), knee (n,), r_out, t_out of knea_select.hip: KnEA's knee points of the fronts up to the critical one and its cut
+std::vector<at::Tensor> knea_select(const at::Tensor& obj, const at::Tensor& rank, int64_t N, const at::Tensor& r, const at::Tensor& t,
+                                    double knee_rate) {
+  CHECK_DEV(obj); CHECK_F32(obj); CHECK_CONTIG(obj); CHECK_DEV(rank); CHECK_CONTIG(rank); CHECK_DEV(r); CHECK_DEV(t);
+  TORCH_CHECK(obj.dim() == 2, "knea_select: obj float32 (n, m)");
+  const int64_t n = obj.size(0), m = obj.size(1);
+  TORCH_CHECK((rank.scalar_type() == at::kInt || rank.scalar_type() == at::kLong) && rank.dim() == 1 && rank.numel() == n,
+              "knea_select: rank int32 or int64 (n,)");
+  TORCH_CHECK(r.scalar_type() == at::kDouble && r.numel() == 1 && t.scalar_type() == at::kDouble && t.numel() == 1,
+              "knea_select: r and t are one float64 device word each");
+  TORCH_CHECK(rank.device() == obj.device() && r.device() == obj.device() && t.device() == obj.device(), "knea_select: one device");
+  TORCH_CHECK(n >= 2 && n <= 8192, "knea_select: 2 <= n <= 8192");
+  TORCH_CHECK(m >= 1 && m <= 16, "knea_select: 1 <= m <= 16");
+  TORCH_CHECK(N >= 1 && N < n, "knea_select: need 1 <= N < n");
+  TORCH_CHECK(knee_rate > 0.0, "knea_select: knee_rate > 0");
+  c10::DeviceGuard g(obj.device());
+  auto idx = at::empty({N}, obj.options().dtype(at::kLong));
+  auto knee = at::empty({n}, obj.options().dtype(at::kBool));
+  auto r_out = at::empty({}, obj.options().dtype(at::kDouble));
+  auto t_out = at::empty({}, obj.options().dtype(at::kDouble));
+  evx_knea_select(obj.data_ptr<float>(), rank.data_ptr(), rank.scalar_type() == at::kLong ? 1 : 0, (int)n, (int)m, (int)N, knee_rate,
+                  r.data_ptr<double>(), t.data_ptr<double>(), idx.data_ptr<int64_t>(), knee.data_ptr<bool>(), r_out.data_ptr<double>(),
+                  t_out.data_ptr<double>(), cur_stream());
+  return {idx, knee, r_out, t_out};
+}
+
 at::Tensor sra_rank(const at::Tensor& I1, const at::Tensor& I2, const at::Tensor& u, const at::Tensor& pc) {
   CHECK_DEV(I1); CHECK_F32(I1); CHECK_CONTIG(I1); CHECK_DEV(I2); CHECK_F32(I2); CHECK_CONTIG(I2);
   CHECK_DEV(u); CHECK_F32(u); CHECK_CONTIG(u); CHECK_DEV(pc); CHECK_F32(pc);
@@ -1818,6 +1844,7 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("nsga_select(Tensor rank, Tensor f, int N, int mask_pos) -> Tensor");
   m.def("nsga3_niche_select(Tensor rank, Tensor last_rank, Tensor group, Tensor group_dist, Tensor key, int N, int R) -> Tensor");
   m.def("m2m_select(Tensor obj, Tensor region, Tensor rad, int K, int S) -> Tensor[]");
+  m.def("knea_select(Tensor obj, Tensor rank, int N, Tensor r, Tensor t, float knee_rate) -> Tensor[]");
   m.def("sra_rank(Tensor I1, Tensor I2, Tensor u, Tensor pc) -> Tensor");
   m.def("sra_indicators(Tensor obj) -> Tensor[]");
   m.def("ibea_fitness(Tensor obj_norm, float kappa) -> Tensor[]");
@@ -1918,6 +1945,7 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("nsga_select", &nsga_select);
   m.impl("nsga3_niche_select", &nsga3_niche_select);
   m.impl("m2m_select", &m2m_select);
+  m.impl("knea_select", &knea_select);
   m.impl("sra_rank", &sra_rank);
   m.impl("sra_indicators", &sra_indicators);
   m.impl("ibea_fitness", &ibea_fitness);

@@ -238,6 +238,11 @@ void evx_nsga3_niche_select(const int32_t* rank, const int32_t* last_rank, const
 // region is (n,) int64 when region64 else int32, part (K·S,) region-major, counts and worst (K,)
 void evx_m2m_select(const float* f, const void* region, int region64, const int64_t* rad, int n, int m, int K, int S,
                     int64_t* part, int32_t* counts, int32_t* worst, hipStream_t s);
+// knea_select.hip: KnEA's knee points of every front up to the critical one and its cut, one workgroup (n ≤ 8192, m ≤ 16,
+// 1 ≤ N < n); rank is (n,) sorted non-decreasing, int64 when rank64 else int32; r and t are one float64 device word each,
+// read from r_in, t_in and written to r_out, t_out; idx (N,) ascending survivors, knee (n,)
+void evx_knea_select(const float* f, const void* rank, int rank64, int n, int m, int N, double knee_rate, const double* r_in,
+                     const double* t_in, int64_t* idx, bool* knee, double* r_out, double* t_out, hipStream_t s);
 // sra_select.hip: SRA's stochastic ranking (n ≤ evx_sra_rank_max_n(), pc one device word, rank (n,) best first)
 // and its two indicators in one pass (m ≤ evx_sra_indicators_max_m())
 int evx_sra_rank_max_n();
