@@ -1515,6 +1515,70 @@ std::vector<at::Tensor> knea_select(const at::Tensor& obj, const at::Tensor& ran
   return {idx, knee, r_out, t_out};
 }
 
+// rvea_select.hip: the shared argument checks of rvea_cos_best and rvea_select (A (n, m), B (k, m), shift (m) or none)
+void rvea_check(const char* op, const at::Tensor& A, const c10::optional<at::Tensor>& shift, const at::Tensor& B) {
+  CHECK_DEV(A); CHECK_F32(A); CHECK_CONTIG(A); CHECK_DEV(B); CHECK_F32(B); CHECK_CONTIG(B);
+  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.size(1) == B.size(1), op, ": A float32 (n, m), B float32 (k, m)");
+  TORCH_CHECK(A.size(1) >= 1 && A.size(1) <= 16, op, ": 1 <= m <= 16");
+  TORCH_CHECK(A.size(0) >= 1 && A.size(0) <= 32768 && B.size(0) >= 1 && B.size(0) <= 32768, op, ": 1 <= n, k <= 32768");
+  TORCH_CHECK(B.device() == A.device(), op, ": one device");
+  if (shift.has_value() && shift->defined())
+    TORCH_CHECK(shift->numel() == A.size(1) && shift->device() == A.device(), op, ": shift float32 (m,) on the device of A");
+}
+
+// best (n,) float64 and arg (n,) int32 of rvea_select.hip: the largest cosine of every row of A to a row of B and its first position
+std::vector<at::Tensor> rvea_cos_best(const at::Tensor& A, const c10::optional<at::Tensor>& shift, c10::optional<double> floor,
+                                      const at::Tensor& B, bool clamp, bool self_zero) {
+  rvea_check("rvea_cos_best", A, shift, B);
+  const int64_t n = A.size(0), k = B.size(0), m = A.size(1);
+  TORCH_CHECK(!self_zero || n == k, "rvea_cos_best: self_zero needs A = B");
+  const float* sh = optf(shift);
+  c10::DeviceGuard g(A.device());
+  auto bn = at::empty({m, k}, A.options().dtype(at::kDouble));
+  auto best = at::empty({n}, A.options().dtype(at::kDouble));
+  auto arg = at::empty({n}, A.options().dtype(at::kInt));
+  evx_rvea_prepare(B.data_ptr<float>(), (int)k, (int)m, bn.data_ptr<double>(), nullptr, nullptr, 0, cur_stream());
+  evx_rvea_cos_best(A.data_ptr<float>(), sh, floor.has_value() ? 1 : 0, floor.value_or(0.0), bn.data_ptr<double>(), (int)n, (int)k, (int)m,
+                    clamp ? 1 : 0, self_zero ? 1 : 0, 0, nullptr, nullptr, best.data_ptr<double>(), arg.data_ptr<int>(), nullptr, nullptr,
+                    cur_stream());
+  return {best, arg};
+}
+
+// next_ind (nv,) int64, empty (nv,) bool, then arg (n,) int32, apd (n,) and gamma (nv,) float64 of rvea_select.hip: the APD selection
+// of the rows f (n, m) on the vectors v (nv, m); theta is one float32 device word
+std::vector<at::Tensor> rvea_select(const at::Tensor& f, const c10::optional<at::Tensor>& shift, c10::optional<double> floor,
+                                    const at::Tensor& v, const at::Tensor& theta) {
+  rvea_check("rvea_select", f, shift, v);
+  CHECK_DEV(theta); CHECK_F32(theta);
+  TORCH_CHECK(theta.numel() == 1 && theta.device() == f.device(), "rvea_select: theta is one float32 word on the device of f");
+  const int64_t n = f.size(0), nv = v.size(0), m = f.size(1);
+  const float* sh = optf(shift);
+  c10::DeviceGuard g(f.device());
+  auto f64 = f.options().dtype(at::kDouble);
+  auto bn = at::empty({m, nv}, f64);
+  auto gamma = at::empty({nv}, f64);
+  auto vbest = at::empty({nv}, f64);
+  auto varg = at::empty({nv}, f.options().dtype(at::kInt));
+  auto best = at::empty({n}, f64);
+  auto apd = at::empty({n}, f64);
+  auto arg = at::empty({n}, f.options().dtype(at::kInt));
+  auto key = at::empty({nv}, f.options().dtype(at::kLong));
+  auto pick = at::empty({nv}, f.options().dtype(at::kInt));
+  auto next_ind = at::empty({nv}, f.options().dtype(at::kLong));
+  auto empty = at::empty({nv}, f.options().dtype(at::kBool));
+  uint64_t* kp = reinterpret_cast<uint64_t*>(key.data_ptr<int64_t>());
+  hipStream_t s = cur_stream();
+  evx_rvea_prepare(v.data_ptr<float>(), (int)nv, (int)m, bn.data_ptr<double>(), kp, pick.data_ptr<int>(), (int)nv, s);
+  evx_rvea_cos_best(v.data_ptr<float>(), nullptr, 0, 0.0, bn.data_ptr<double>(), (int)nv, (int)nv, (int)m, 1, 1, 1, nullptr, nullptr,
+                    vbest.data_ptr<double>(), varg.data_ptr<int>(), gamma.data_ptr<double>(), nullptr, s);
+  evx_rvea_cos_best(f.data_ptr<float>(), sh, floor.has_value() ? 1 : 0, floor.value_or(0.0), bn.data_ptr<double>(), (int)n, (int)nv, (int)m, 1, 0,
+                    2, gamma.data_ptr<double>(), theta.data_ptr<float>(), best.data_ptr<double>(), arg.data_ptr<int>(), apd.data_ptr<double>(),
+                    kp, s);
+  evx_rvea_pick(arg.data_ptr<int>(), apd.data_ptr<double>(), (int)n, (int)nv, kp, pick.data_ptr<int>(), next_ind.data_ptr<int64_t>(),
+                empty.data_ptr<bool>(), s);
+  return {next_ind, empty, arg, apd, gamma};
+}
+
 at::Tensor sra_rank(const at::Tensor& I1, const at::Tensor& I2, const at::Tensor& u, const at::Tensor& pc) {
   CHECK_DEV(I1); CHECK_F32(I1); CHECK_CONTIG(I1); CHECK_DEV(I2); CHECK_F32(I2); CHECK_CONTIG(I2);
   CHECK_DEV(u); CHECK_F32(u); CHECK_CONTIG(u); CHECK_DEV(pc); CHECK_F32(pc);
@@ -1845,6 +1909,8 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("nsga3_niche_select(Tensor rank, Tensor last_rank, Tensor group, Tensor group_dist, Tensor key, int N, int R) -> Tensor");
   m.def("m2m_select(Tensor obj, Tensor region, Tensor rad, int K, int S) -> Tensor[]");
   m.def("knea_select(Tensor obj, Tensor rank, int N, Tensor r, Tensor t, float knee_rate) -> Tensor[]");
+  m.def("rvea_cos_best(Tensor A, Tensor? shift, float? floor, Tensor B, bool clamp, bool self_zero) -> Tensor[]");
+  m.def("rvea_select(Tensor f, Tensor? shift, float? floor, Tensor v, Tensor theta) -> Tensor[]");
   m.def("sra_rank(Tensor I1, Tensor I2, Tensor u, Tensor pc) -> Tensor");
   m.def("sra_indicators(Tensor obj) -> Tensor[]");
   m.def("ibea_fitness(Tensor obj_norm, float kappa) -> Tensor[]");
@@ -1946,6 +2012,8 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("nsga3_niche_select", &nsga3_niche_select);
   m.impl("m2m_select", &m2m_select);
   m.impl("knea_select", &knea_select);
+  m.impl("rvea_cos_best", &rvea_cos_best);
+  m.impl("rvea_select", &rvea_select);
   m.impl("sra_rank", &sra_rank);
   m.impl("sra_indicators", &sra_indicators);
   m.impl("ibea_fitness", &ibea_fitness);

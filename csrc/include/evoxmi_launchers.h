@@ -243,6 +243,17 @@ void evx_m2m_select(const float* f, const void* region, int region64, const int6
 // read from r_in, t_in and written to r_out, t_out; idx (N,) ascending survivors, knee (n,)
 void evx_knea_select(const float* f, const void* rank, int rank64, int n, int m, int N, double knee_rate, const double* r_in,
                      const double* t_in, int64_t* idx, bool* knee, double* r_out, double* t_out, hipStream_t s);
+// rvea_select.hip: the RVEA family's selection (m ≤ 16; the contract is in evoxmi/ops/rvea.py).  prepare: bn (m, k) float64 the
+// normalised rows of B, and, when key is given, the reset of the pick's key and pick words (nkey each).  cos_best: for every row
+// of A (shifted, floored) the largest cosine to a row of bn and the first position that holds it; mode 1 also writes
+// aux = acos(best), mode 2 aux = apd from gamma (k,) and the float32 device word theta, folding each row's apd into key.
+// pick: next_ind and empty (nv,) from arg, apd (n,) and the folded key
+void evx_rvea_prepare(const float* B, int k, int m, double* bn, uint64_t* key, int* pick, int nkey, hipStream_t s);
+void evx_rvea_cos_best(const float* A, const float* shift, int has_floor, double floor_v, const double* bn, int n, int k, int m, int clamp,
+                       int self_zero, int mode, const double* gamma, const float* theta, double* best, int* arg, double* aux, uint64_t* key,
+                       hipStream_t s);
+void evx_rvea_pick(const int* arg, const double* apd, int n, int nv, const uint64_t* key, int* pick, int64_t* next_ind, bool* empty,
+                   hipStream_t s);
 // sra_select.hip: SRA's stochastic ranking (n ≤ evx_sra_rank_max_n(), pc one device word, rank (n,) best first)
 // and its two indicators in one pass (m ≤ evx_sra_indicators_max_m())
 int evx_sra_rank_max_n();

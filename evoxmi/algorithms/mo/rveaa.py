@@ -4,6 +4,10 @@ A second set of reference vectors is regenerated at random wherever no
 non-dominated solution is associated; the population has 2N NaN-padded slots; on
 the penultimate generation the survivors are batch-truncated to N by removing the
 most crowded (largest maximum cosine to another solution).
+
+The associations are ``ops.rvea.cos_best`` (``rvea_select.hip`` on a device).  On a device the truncated pair is computed
+every generation and chosen with a predicate on ``state.gen``, so ``tell`` reads nothing on the host and a generation
+is capturable; on the CPU the truncation runs in its generation only.
 """
 from __future__ import annotations
 
@@ -14,14 +18,14 @@ from ...operators import selection
 from ...operators.sampling import UniformSampling
 from ...operators.selection.non_dominate import non_dominated_sort
 from ...ops import random as rnd
-from ...utils.common import cos_dist
+from ...ops import rvea as rvea_ops
 from .common import MOAlgorithm
 
 
 def rv_regeneration(pop_obj, v, key):
-    obj = pop_obj - torch.nan_to_num(pop_obj, nan=float("inf")).min(0).values
-    cosine = torch.nan_to_num(cos_dist(obj, v), nan=-float("inf"))
-    assoc = torch.argmax(cosine, 1)
+    colmin = torch.nan_to_num(pop_obj, nan=float("inf")).min(0).values
+    obj = pop_obj - colmin
+    assoc = rvea_ops.cos_best(pop_obj, v, shift=colmin)[1].clamp(min=0)  # a NaN row's −1: it adds 0 below
     valid_row = ~torch.isnan(pop_obj).any(1)
     hit = torch.zeros(v.shape[0], device=v.device).scatter_add_(0, assoc, valid_row.to(torch.float32))
     rand = rnd.uniform(key, tuple(v.shape)).to(v.device) * torch.nan_to_num(obj, nan=-float("inf")).max(0).values
@@ -30,12 +34,10 @@ def rv_regeneration(pop_obj, v, key):
 
 def batch_truncation(pop, obj):
     n = pop.shape[0] // 2
-    cosine = cos_dist(obj, obj)
-    cosine = cosine.masked_fill(torch.eye(cosine.shape[0], dtype=torch.bool, device=obj.device), 0)
-    top = torch.nan_to_num(cosine, nan=-float("inf")).max(1).values  # most similar neighbour
+    top = rvea_ops.cos_best(obj, obj, self_zero=True)[0]  # most similar neighbour
     worst = torch.argsort(-top, stable=True)[:n]  # most crowded first (NaN rows last)
-    keep = torch.ones(pop.shape[0], dtype=torch.bool, device=pop.device)
-    keep[worst] = False
+    # index_fill_, not keep[worst] = False: the indexed assignment of a Python scalar copies it from the host (no capture)
+    keep = torch.ones(pop.shape[0], dtype=torch.bool, device=pop.device).index_fill_(0, worst, False)
     nan = torch.full_like(pop, float("nan"))
     return torch.where(keep[:, None], pop, nan), torch.where(keep[:, None], obj, torch.full_like(obj, float("nan")))
 
@@ -85,6 +87,11 @@ class RVEAa(MOAlgorithm):
         span = torch.nan_to_num(surv_fit, nan=-float("inf")).max(0).values - torch.nan_to_num(surv_fit, nan=float("inf")).min(0).values
         v_adapt = torch.where((gen % period) == 0, state.init_v * span, v[:N])
         v = torch.cat([v_adapt, rv_regeneration(surv_fit, v[N:], sub)])
-        if int(gen) + 1 == self.max_gen:
+        if surv_fit.device.type != "cpu":
+            # a device predicate on the state's own gen: no host read, and it cannot drift from state.gen after a restore
+            last = (gen + 1) == self.max_gen
+            cut, cut_fit = batch_truncation(surv, surv_fit)
+            surv, surv_fit = torch.where(last, cut, surv), torch.where(last, cut_fit, surv_fit)
+        elif int(gen) + 1 == self.max_gen:
             surv, surv_fit = batch_truncation(surv, surv_fit)
         return state.update(population=surv, fitness=surv_fit, reference_vector=v, gen=gen, key=key)

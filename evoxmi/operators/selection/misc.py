@@ -9,7 +9,7 @@ import torch
 from evoxmi.ops.sort import topk as _topk
 
 from ...ops import random as rnd
-from ...utils.common import cos_dist
+from ...ops import rvea as _rvea
 
 
 def move_n_small_numbers(a: torch.Tensor, n):
@@ -103,25 +103,9 @@ class RouletteWheelSelection:
 
 def ref_vec_guided(x, f, v, theta):
     """RVEA angle-penalised distance selection (reference ``rvea_selection.py:9-54``).
-    Rows of ``x``/``f`` may be NaN padding; empty reference vectors yield NaN rows."""
-    n, m = f.shape
-    nv = v.shape[0]
-    obj = f - torch.nan_to_num(f, nan=float("inf")).min(0).values
-    obj = torch.clamp(obj, min=1e-32)
-    cosine = cos_dist(v, v)
-    cosine = cosine.masked_fill(torch.eye(nv, dtype=torch.bool, device=v.device), 0)
-    cosine = cosine.clamp(0, 1)
-    gamma = torch.arccos(cosine).min(1).values
-    angle = torch.arccos(cos_dist(torch.nan_to_num(obj, nan=0.0), v).clamp(0, 1))
-    nan_mask = torch.isnan(obj).any(1)
-    associate = torch.argmin(angle, 1)
-    associate = torch.where(nan_mask, torch.full_like(associate, -1), associate)
-    norm = torch.sqrt((torch.nan_to_num(obj, nan=0.0) ** 2).sum(1))
-    member = associate[:, None] == torch.arange(nv, device=v.device)[None, :]  # (n, nv)
-    apd = (1 + m * theta * angle / gamma[None, :]) * norm[:, None]
-    apd = torch.where(member, apd, torch.full_like(apd, float("inf")))
-    next_ind = torch.argmin(apd, 0)
-    empty = ~member.any(0)
+    Rows of ``x``/``f`` may be NaN padding; empty reference vectors yield NaN rows.  The association and the pick are
+    ``ops.rvea.select``: HIP kernels in float64 on a device, the dense float32 expressions on the CPU."""
+    next_ind, empty = _rvea.select(f, v, theta)
     nan_row = torch.full((1,), float("nan"), device=x.device, dtype=x.dtype)
     next_x = torch.where(empty[:, None], nan_row, x[next_ind])
     next_f = torch.where(empty[:, None], nan_row, f[next_ind])

@@ -81,8 +81,9 @@ def _run(cmd):
 # beside MFMAs costs ≈13 cycles more than two v_sub_f32)
 # knea_select.hip: its contract is float64 arithmetic in a stated operation order with no FMA, so a
 # host implementation of the same operations reproduces its keys and box tests bit for bit
+# rvea_select.hip: the same kind of contract: its cosines are symmetric bit for bit and a host implementation reproduces them
 FILE_FLAGS = {"eigh_sbr.hip": ["-fno-slp-vectorize"], "mo_geom.hip": ["-ffp-contract=fast-honor-pragmas"],
-              "knea_select.hip": ["-ffp-contract=off"],
+              "knea_select.hip": ["-ffp-contract=off"], "rvea_select.hip": ["-ffp-contract=off"],
               "rng.hip": ["-ffp-contract=fast-honor-pragmas"],
               "neuro.hip": ["-fno-slp-vectorize"], "gemm_ks.hip": ["-fno-slp-vectorize"]}
 
