@@ -1098,6 +1098,40 @@ std::vector<at::Tensor> ant_rollout(const at::Tensor& W, int64_t h1, int64_t h2,
   return {ret, steps};
 }
 
+// model: the float32 table of PlanarChain.model_table(), in host memory (it travels by value in the kernel arguments)
+std::vector<at::Tensor> planar_rollout(const at::Tensor& W, int64_t h1, int64_t h2, const at::Tensor& model, const at::Tensor& init,
+                                       int64_t cap) {
+  CHECK_DEV(W); CHECK_F32(W); CHECK_CONTIG(W); CHECK_DEV(init); CHECK_F32(init); CHECK_CONTIG(init);
+  CHECK_F32(model); CHECK_CONTIG(model);
+  TORCH_CHECK(model.device().is_cpu(), "planar_rollout: the model table must be a CPU tensor");
+  TORCH_CHECK(model.numel() == evx_planar_table_words(), "planar_rollout: the model table has ", model.numel(), " words, expected ",
+              evx_planar_table_words());
+  TORCH_CHECK(W.dim() == 2, "planar_rollout: W must be (N, P)");
+  TORCH_CHECK(h1 >= 1 && h1 <= 512 && h2 >= 1 && h2 <= 512, "planar_rollout: hidden sizes in [1, 512]");
+  const float* mt = model.data_ptr<float>();
+  const float nbf = mt[0], skipf = mt[1], subf = mt[2];
+  TORCH_CHECK(nbf >= 2 && nbf <= 8 && nbf == (float)(int)nbf, "planar_rollout: 2 to 8 bodies, got ", nbf);
+  const int64_t nb = (int64_t)nbf, nd = nb + 2, na = nb - 1;
+  TORCH_CHECK(nd <= 10, "planar_rollout: at most 10 degrees of freedom, got ", nd);
+  TORCH_CHECK(skipf >= 0 && skipf <= 3 && skipf == (float)(int)skipf, "planar_rollout: obs_skip in [0, 3]");
+  TORCH_CHECK(subf >= 1 && subf <= 64 && subf == (float)(int)subf, "planar_rollout: 1 to 64 sub-steps per control step");
+  const int64_t no = 2 * nd - (int64_t)skipf;
+  TORCH_CHECK(no <= 32 && na <= 8, "planar_rollout: at most 32 observations and 8 actions");
+  TORCH_CHECK(evx_planar_supported(mt) == 0,
+              "planar_rollout: no kernel is instantiated for this tree shape (chains of 3 or 4 bodies, or a root with two chains of 3)");
+  const int64_t P = no * h1 + h1 + h1 * h2 + h2 + h2 * na + na;
+  TORCH_CHECK(W.size(1) == P, "planar_rollout: W has ", W.size(1), " columns, MLP ", no, "-", h1, "-", h2, "-", na, " needs ", P);
+  TORCH_CHECK(init.numel() == 2 * nd, "planar_rollout: init state must have ", 2 * nd, " entries");
+  TORCH_CHECK((P + 32 + h1 + h2 + 8) * 4 <= 160 * 1024, "planar_rollout: MLP too large for one wave's LDS");
+  c10::DeviceGuard g(W.device());
+  const int64_t N = W.size(0);
+  auto ret = at::empty({N}, W.options());
+  auto steps = at::empty({N}, W.options().dtype(at::kInt));
+  if (N > 0) evx_planar_rollout(W.data_ptr<float>(), P, (int)N, (int)h1, (int)h2, mt, init.data_ptr<float>(), (int)cap, ret.data_ptr<float>(),
+                                steps.data_ptr<int>(), cur_stream());
+  return {ret, steps};
+}
+
 // rows > 0: only the parents of offspring row0 .. row0+rows−1 (the rest of p0 / p1 zero)
 std::vector<at::Tensor> moead_parents(const at::Tensor& nb, const at::Tensor& key, int64_t row0, int64_t rows) {
   CHECK_DEV(nb); CHECK_CONTIG(nb); check_key(key);
@@ -1873,6 +1907,7 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("pm(Tensor x, Tensor lb, Tensor ub, Tensor keys, float pro_m, float dis_m, int nm, int col0=0, int dtot=0) -> Tensor");
   m.def("nds(Tensor f, int limit=0, Tensor? err=None) -> Tensor");
   m.def("ant_rollout(Tensor W, int h1, int h2, Tensor init, int cap) -> Tensor[]");
+  m.def("planar_rollout(Tensor W, int h1, int h2, Tensor model, Tensor init, int cap) -> Tensor[]");
   m.def("stochastic_ranking(Tensor I1, Tensor I2, Tensor rnd, float pc) -> Tensor");
   m.def("moead_scan(Tensor objs, Tensor off_objs, Tensor P, Tensor W, Tensor z, int func, int nr, int update_z) -> Tensor[]");
   m.def("de_trial(Tensor P, Tensor idx, Tensor coef, Tensor cur, Tensor mode, Tensor CR, Tensor jr, Tensor L, Tensor key, Tensor lb, Tensor ub, int repair, Tensor err, int col0=0, int d_total=0) -> Tensor");
@@ -1973,6 +2008,7 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("pm", &pm);
   m.impl("nds", &nds);
   m.impl("ant_rollout", &ant_rollout);
+  m.impl("planar_rollout", &planar_rollout);
   m.impl("moead_scan", &moead_scan);
   m.impl("de_trial", &de_trial);
   m.impl("dtlz", &dtlz);

@@ -1,4 +1,5 @@
-"""Launcher of the persistent Ant + MLP rollout kernel (``neuro.hip``)."""
+"""Launchers of the persistent rollout kernels: Ant + MLP (``neuro.hip``) and the planar
+articulated-tree tasks + MLP (``planar_rollout.hip``)."""
 from __future__ import annotations
 
 import torch
@@ -16,3 +17,30 @@ def ant_rollout(flat_weights: torch.Tensor, h1: int, h2: int, init_state: torch.
     W3 (h2×8), b3], all starting from ``init_state`` (29,)."""
     return _ext.ops().ant_rollout(flat_weights.to(torch.float32).contiguous(), int(h1), int(h2),
                                   init_state.to(device=flat_weights.device, dtype=torch.float32).contiguous(), int(cap))
+
+
+def planar_param_count(obs_dim: int, h1: int, h2: int, act_dim: int) -> int:
+    return obs_dim * h1 + h1 + h1 * h2 + h2 + h2 * act_dim + act_dim
+
+
+PLANAR_LDS_LIMIT = 160 * 1024  # one wave's share of LDS, in bytes
+
+
+def planar_lds_bytes(obs_dim: int, h1: int, h2: int, act_dim: int) -> int:
+    """LDS one wave of ``planar_rollout`` needs: weights, 32 spare words and the activations; the binding
+    refuses a policy that needs more than ``PLANAR_LDS_LIMIT``."""
+    return (planar_param_count(obs_dim, h1, h2, act_dim) + 32 + h1 + h2 + 8) * 4
+
+
+def planar_rollout(flat_weights: torch.Tensor, h1: int, h2: int, model: torch.Tensor, init_state: torch.Tensor, cap: int):
+    """Episode returns (N,) float32 and lengths (N,) int32 of N individuals on a planar
+    articulated-tree model.  ``model`` is the float32 table of ``PlanarChain.model_table()`` (kept
+    in host memory: it is passed to the kernel by value, so the launch captures into a hipGraph);
+    the MLP obs-h1-h2-act (tanh) weights are rows of ``flat_weights`` in the layout [W1 (obs×h1),
+    b1, W2 (h1×h2), b2, W3 (h2×act), b3]; every individual starts from ``init_state`` (2·nd,) =
+    q ++ u.  Raises for a model or policy outside the kernel's caps (≤ 8 bodies, ≤ 10 degrees of
+    freedom, ≤ 32 observations, ≤ 8 actions, hidden ≤ 512, ``planar_lds_bytes`` ≤ ``PLANAR_LDS_LIMIT``, a
+    supported tree shape)."""
+    return _ext.ops().planar_rollout(flat_weights.to(torch.float32).contiguous(), int(h1), int(h2),
+                                     model.to(device="cpu", dtype=torch.float32).contiguous(),
+                                     init_state.to(device=flat_weights.device, dtype=torch.float32).contiguous(), int(cap))

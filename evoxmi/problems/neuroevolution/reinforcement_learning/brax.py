@@ -11,6 +11,11 @@ Execution paths:
 * **fused** (``"ant"`` + :class:`~evoxmi.models.MLPPolicy` 27-h1-h2-8 tanh, on a GPU):
   one persistent HIP kernel runs whole episodes with each individual's weights held
   in LDS (``ops.neuro.ant_rollout``);
+* **fused, planar** (``"hopper"``, ``"walker2d"``, ``"halfcheetah"``, ``"swimmer"`` or any
+  :class:`~.planar.PlanarChain` within the kernel's caps + a 3-layer tanh/tanh
+  :class:`~evoxmi.models.MLPPolicy` of matching sizes with hidden ≤ 512 whose weights fit one wave's
+  share of LDS (hidden up to about 190), on a GPU): the
+  table-driven persistent kernel ``ops.neuro.planar_rollout``;
 * **generic**: a device-resident loop of batched policy forward + batched env step;
   the all-done early exit is checked every ``check_every`` steps to avoid per-step
   host synchronisation.
@@ -29,6 +34,7 @@ from ....core import Problem, State
 from ....models.mlp import MLPPolicy
 from ....ops import neuro as neuro_ops
 from .envs import Ant, get_environment
+from .planar import MAX_HIDDEN, PlanarChain
 
 
 class Brax(Problem):
@@ -42,11 +48,22 @@ class Brax(Problem):
         self.fused = fused
         self.check_every = check_every
         self._s0 = None
+        self._table = None
 
     def setup(self, key):
         return State(key=key)
 
+    def _planar_ok(self, weights):
+        p, env = self.policy, self.env
+        return (self.fused and isinstance(env, PlanarChain) and env.within_caps() and isinstance(p, MLPPolicy) and len(p.sizes) == 4
+                and p.sizes[0] == env.obs_dim and p.sizes[-1] == env.act_dim and max(p.sizes[1:3]) <= MAX_HIDDEN
+                and neuro_ops.planar_lds_bytes(*p.sizes) <= neuro_ops.PLANAR_LDS_LIMIT
+                and p.activation == "tanh" and p.output_activation == "tanh" and isinstance(weights, dict)
+                and all(x.is_cuda and x.dtype == torch.float32 for x in torch.utils._pytree.tree_leaves(weights)))
+
     def _fused_ok(self, weights):
+        if isinstance(self.env, PlanarChain):
+            return self._planar_ok(weights)
         return (self.fused and isinstance(self.env, Ant) and isinstance(self.policy, MLPPolicy) and len(self.policy.sizes) == 4
                 and self.policy.sizes[0] == 27 and self.policy.sizes[-1] == 8 and self.policy.activation == "tanh"
                 and self.policy.output_activation == "tanh" and isinstance(weights, dict)
@@ -67,7 +84,16 @@ class Brax(Problem):
         return s0
 
     def evaluate(self, state, weights):
-        if self._fused_ok(weights):
+        planar = isinstance(self.env, PlanarChain)
+        if planar and self._planar_ok(weights):
+            w = self.policy.flat(weights)
+            s0 = self._initial_state(state.key, w.device)
+            if self._table is None:
+                self._table = self.env.model_table()
+            ret, steps = neuro_ops.planar_rollout(w, self.policy.sizes[1], self.policy.sizes[2], self._table, s0, self.cap_episode)
+            self.last_episode_lengths = steps  # diagnostics only (not part of the state)
+            return ret, state
+        if not planar and self._fused_ok(weights):
             w = self.policy.flat(weights)
             s0 = self._initial_state(state.key, w.device)
             h1, h2 = self.policy.sizes[1], self.policy.sizes[2]
@@ -80,8 +106,10 @@ class Brax(Problem):
         s, obs = s.to(dev), obs.to(dev)
         total = torch.zeros(n, device=dev)
         alive = torch.ones(n, dtype=torch.bool, device=dev)
+        # a float64 weight tree gets float64 observations (the environments reset in float32)
+        wdt = leaves[0].dtype if leaves[0].is_floating_point() else obs.dtype
         for t in range(self.cap_episode):
-            act = self.policy(weights, obs)
+            act = self.policy(weights, obs.to(wdt))
             s, obs, r, done = self.env.step(s, act)
             alive = alive & ~done
             total = total + alive.to(total.dtype) * r
@@ -91,7 +119,11 @@ class Brax(Problem):
 
     def visualize(self, key, weights, output_type: str = "trajectory", respect_done=False, **kwargs):
         """Roll out one policy and return its state trajectory (list of (state_dim,)
-        tensors); Brax's HTML renderer is not available here."""
+        tensors); Brax's HTML renderer is not available here.  ``output_type="rgb_array"``
+        returns the trajectory as ``(H, W, 3) uint8`` frames instead, for environments that
+        have ``render`` (``kwargs`` go to it, e.g. ``width`` / ``height``)."""
+        if output_type == "rgb_array" and not hasattr(self.env, "render"):
+            raise ValueError(f"visualize: environment {self.env_name!r} has no render()")
         s, obs = self.env.reset(key.cpu(), 1)
         traj = [s[0].clone()]
         for _ in range(self.cap_episode):
@@ -100,4 +132,6 @@ class Brax(Problem):
             traj.append(s[0].clone())
             if respect_done and bool(done[0]):
                 break
+        if output_type == "rgb_array":
+            return [self.env.render(x, **kwargs) for x in traj]
         return traj

@@ -25,6 +25,8 @@ that keeps each individual's MLP weights in LDS for the whole episode.
   angular velocity, 8 joint velocities (Brax ``qpos[2:] ++ qvel``).  Reward = forward
   velocity + 1 (healthy) − 0.5‖a‖²; the episode ends when torso z leaves [0.2, 1.0].
   Reference behaviour: ``src/evox/problems/neuroevolution/reinforcement_learning/brax.py:51-73``.
+* ``hopper``, ``walker2d``, ``halfcheetah``, ``swimmer`` — the planar Brax-style tasks on the
+  table-driven articulated-tree engine of :mod:`.planar` (fused rollout: ``ops.neuro.planar_rollout``).
 """
 from __future__ import annotations
 
@@ -48,7 +50,8 @@ def register(name):
 def get_environment(env_name: str, **kwargs):
     key = env_name.lower().replace("-v1", "").replace("-v0", "").replace("-v4", "").replace("-v5", "")
     aliases = {"cartpole": "cartpole", "pendulum": "pendulum", "mountaincarcontinuous": "mountain_car_continuous",
-               "mountain_car_continuous": "mountain_car_continuous", "ant": "ant"}
+               "mountain_car_continuous": "mountain_car_continuous", "ant": "ant", "hopper": "hopper", "walker2d": "walker2d",
+               "halfcheetah": "halfcheetah", "swimmer": "swimmer"}
     if key not in aliases:
         raise ValueError(f"unknown environment {env_name!r}; native environments: {sorted(ENVS)}")
     return ENVS[aliases[key]](**kwargs)
@@ -427,3 +430,6 @@ class Ant:
         healthy = (z >= 0.2) & (z <= 1.0)
         reward = (s[:, 0] - x0) / (P["dt"] * P["substeps"]) + healthy.to(s.dtype) - 0.5 * (a * a).sum(1)
         return s, self.obs(s), reward, ~healthy
+
+
+from . import planar  # noqa: E402,F401  (registers hopper, walker2d, halfcheetah, swimmer)

@@ -1,6 +1,7 @@
-"""OpenES + Brax-style Ant throughput (north-star config 4: pop 8192, MLP 27-64-64-8).
+"""OpenES + Brax-style Ant throughput (north-star config 4: pop 8192, MLP 27-64-64-8), or one of the
+planar tasks with --env {hopper,walker2d,halfcheetah,swimmer}.
 
-python tools/bench_neuro.py [--pop 8192] [--cap 1000] [--gens 5]
+python tools/bench_neuro.py [--env ant] [--pop 8192] [--cap 1000] [--gens 5]
 torchrun --nproc-per-node N tools/bench_neuro.py ...   (population sharded over N GPUs:
 each rank rolls out its slice, OpenES all-reduces the partial gradient over RCCL)
 """
@@ -26,6 +27,7 @@ def main():
     ap.add_argument("--pop", type=int, default=8192)
     ap.add_argument("--gpus", type=int, default=1, help="ranks (one per GPU); spawned here unless torchrun started them")
     ap.add_argument("--cap", type=int, default=1000)
+    ap.add_argument("--env", default="ant", choices=["ant", "hopper", "walker2d", "halfcheetah", "swimmer"])
     ap.add_argument("--gens", type=int, default=5)
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--wscale", type=float, default=0.1)
@@ -35,6 +37,8 @@ def main():
     ap.add_argument("--per-gen", action="store_true", help="print each generation's wall time and episode lengths")
     ap.add_argument("--dump-pop", default=None, help="save the last generation's population (rollout-probe input)")
     args = ap.parse_args()
+    if args.dump_pop and args.env != "ant":
+        ap.error("--dump-pop re-times the Ant rollout and is only available with --env ant")
     if args.kernel_only:
         return kernel_only(args)
     from evoxmi.parallel import init_distributed
@@ -51,11 +55,14 @@ def main():
         print(f"bench_neuro.py: --gpus {args.gpus} but the job has {world} rank(s)", file=sys.stderr, flush=True)
         sys.exit(2)
     dist_on = world > 1 or args.force_dist
-    policy = MLPPolicy([27, args.hidden, args.hidden, 8])
+    from evoxmi.problems.neuroevolution.reinforcement_learning.envs import get_environment
+
+    env = get_environment(args.env)
+    policy = MLPPolicy([env.obs_dim, args.hidden, args.hidden, env.act_dim])
     params = policy.init(rnd.PRNGKey(0), device=dev)
     tv = TreeAndVector(params)
     algo = OpenES(tv.to_vector(params), args.pop, learning_rate=0.01, noise_stdev=0.05, optimizer="adam")
-    prob = Brax(policy, "ant", args.cap)
+    prob = Brax(policy, args.env, args.cap)
     wf = StdWorkflow(algo, prob, sol_transforms=[tv.batched_to_tree], fit_transforms=[rank_based_fitness],
                      opt_direction="max", graph=args.graph)
     st = wf.init(rnd.PRNGKey(1, device=dev))
@@ -107,7 +114,7 @@ def main():
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
         dist.all_reduce(env_steps)
     dt, env_steps = float(dt), int(env_steps)
-    out = {"pop": args.pop, "n_gpus": dist.get_world_size() if dist.is_initialized() else 1, "cap_episode": args.cap, "params": policy.num_params, "ms_per_gen": round(dt * 1e3, 2),
+    out = {**({} if args.env == "ant" else {"env": args.env}), "pop": args.pop, "n_gpus": dist.get_world_size() if dist.is_initialized() else 1, "cap_episode": args.cap, "params": policy.num_params, "ms_per_gen": round(dt * 1e3, 2),
            "gens_per_sec": round(1 / dt, 3), "env_steps_per_sec": round(env_steps / args.gens / dt, 1),
            "mean_episode_len": round(env_steps / args.gens / args.pop, 1), "graph": args.graph}
     if rank == 0:
@@ -124,23 +131,34 @@ def kernel_only(args):
     from evoxmi.problems.neuroevolution.reinforcement_learning.envs import get_environment
 
     h = args.hidden
-    P = neuro.ant_param_count(h, h)
+    env = get_environment(args.env)
+    if args.env == "ant":
+        P = neuro.ant_param_count(h, h)
+
+        def rollout(W, init):
+            return neuro.ant_rollout(W, h, h, init, args.cap)
+    else:
+        P = neuro.planar_param_count(env.obs_dim, h, h, env.act_dim)
+        table = env.model_table()
+
+        def rollout(W, init):
+            return neuro.planar_rollout(W, h, h, table, init, args.cap)
     g = torch.Generator(device="cuda").manual_seed(0)
     W = args.wscale * torch.randn(args.pop, P, device="cuda", generator=g)
-    s0, _ = get_environment("ant").reset(rnd.PRNGKey(0), 1)
+    s0, _ = env.reset(rnd.PRNGKey(0), 1)
     init = s0[0].cuda()
-    neuro.ant_rollout(W, h, h, init, args.cap)
+    rollout(W, init)
     torch.cuda.synchronize()
     t = time.perf_counter()
     steps = 0
     for _ in range(args.gens):
-        _, st = neuro.ant_rollout(W, h, h, init, args.cap)
+        _, st = rollout(W, init)
         steps += st.sum()
     torch.cuda.synchronize()
     max_len = int(st.max())
     dt = (time.perf_counter() - t) / args.gens
     steps = int(steps) / args.gens
-    print(json.dumps({"mode": "kernel_only", "pop": args.pop, "hidden": h, "cap": args.cap, "ms_per_rollout": round(dt * 1e3, 3),
+    print(json.dumps({"mode": "kernel_only", **({} if args.env == "ant" else {"env": args.env}), "pop": args.pop, "hidden": h, "cap": args.cap, "ms_per_rollout": round(dt * 1e3, 3),
                       "mean_episode_len": round(steps / args.pop, 1), "max_episode_len": max_len,
                       "us_per_step_of_longest": round(dt * 1e6 / max(max_len, 1), 3), "env_steps_per_sec": round(steps / dt, 1)}))
 
