@@ -1111,17 +1111,31 @@ std::vector<at::Tensor> planar_rollout(const at::Tensor& W, int64_t h1, int64_t 
   const float* mt = model.data_ptr<float>();
   const float nbf = mt[0], skipf = mt[1], subf = mt[2];
   TORCH_CHECK(nbf >= 2 && nbf <= 8 && nbf == (float)(int)nbf, "planar_rollout: 2 to 8 bodies, got ", nbf);
-  const int64_t nb = (int64_t)nbf, nd = nb + 2, na = nb - 1;
+  const int64_t nb = (int64_t)nbf, nd = nb + 2;
   TORCH_CHECK(nd <= 10, "planar_rollout: at most 10 degrees of freedom, got ", nd);
   TORCH_CHECK(skipf >= 0 && skipf <= 3 && skipf == (float)(int)skipf, "planar_rollout: obs_skip in [0, 3]");
   TORCH_CHECK(subf >= 1 && subf <= 64 && subf == (float)(int)subf, "planar_rollout: 1 to 64 sub-steps per control step");
-  const int64_t no = 2 * nd - (int64_t)skipf;
+  // a free root with the run task (header words 20 and 21 zero): q ++ u without the skipped entries, every hinge an action;
+  // any other model's observation, action and auxiliary-state sizes come from its instantiation
+  const bool plain = mt[20] == 0.f && mt[21] == 0.f;
+  int64_t no = 2 * nd - (int64_t)skipf, na = nb - 1, naux = 0;
+  const float* slider = mt + 24 + 8 * 16;  // hinge row 0: gear at 0, limit_k at 7
+  const char* no_combination =
+      "planar_rollout: no kernel is instantiated for this combination of tree shape, root constraint, task kind and actuation "
+      "(chain of 2, x-only root, balance; chain of 3, x-only root, balance_tip; chain of 3, locked root, reach)";
+  TORCH_CHECK(!plain || (slider[0] == 0.f && slider[7] == 0.f), no_combination);
+  if (!plain) {
+    int o = 0, a = 0, x = 0;
+    TORCH_CHECK(evx_planar_dims(mt, &o, &a, &x) == 0, no_combination);
+    TORCH_CHECK(skipf == 0, "planar_rollout: obs_skip applies to the run task only");
+    no = o, na = a, naux = x;
+  }
   TORCH_CHECK(no <= 32 && na <= 8, "planar_rollout: at most 32 observations and 8 actions");
   TORCH_CHECK(evx_planar_supported(mt) == 0,
               "planar_rollout: no kernel is instantiated for this tree shape (chains of 3 or 4 bodies, or a root with two chains of 3)");
   const int64_t P = no * h1 + h1 + h1 * h2 + h2 + h2 * na + na;
   TORCH_CHECK(W.size(1) == P, "planar_rollout: W has ", W.size(1), " columns, MLP ", no, "-", h1, "-", h2, "-", na, " needs ", P);
-  TORCH_CHECK(init.numel() == 2 * nd, "planar_rollout: init state must have ", 2 * nd, " entries");
+  TORCH_CHECK(init.numel() == 2 * nd + naux, "planar_rollout: init state must have ", 2 * nd + naux, " entries");
   TORCH_CHECK((P + 32 + h1 + h2 + 8) * 4 <= 160 * 1024, "planar_rollout: MLP too large for one wave's LDS");
   c10::DeviceGuard g(W.device());
   const int64_t N = W.size(0);

@@ -202,6 +202,7 @@ void evx_ant_rollout(const float* W, int64_t P, int N, int h1, int h2, const flo
 // planar_rollout.hip: model = the host-side float32 table of PlanarChain.model_table()
 int evx_planar_table_words();
 int evx_planar_supported(const float* model);
+int evx_planar_dims(const float* model, int* no, int* na, int* naux);
 void evx_planar_rollout(const float* W, int64_t P, int N, int h1, int h2, const float* model, const float* init, int cap, float* ret,
                         int* steps, hipStream_t s);
 size_t evx_nds_workspace_words(int n);

@@ -1,5 +1,6 @@
-// Persistent rollout of the planar articulated-tree tasks (hopper, walker2d, halfcheetah, swimmer
-// and any model of the same tree shapes) with a per-individual MLP policy.
+// Persistent rollout of the planar articulated-tree tasks (hopper, walker2d, halfcheetah, swimmer,
+// inverted_pendulum, inverted_double_pendulum, reacher and any model of the same combinations) with a
+// per-individual MLP policy.
 //
 // Execution model of ant_rollout_kernel (neuro.hip): one wave64 owns one individual for the whole
 // episode, its MLP obs-h1-h2-act (tanh) weights live in LDS with lanes striding over units (the first
@@ -10,9 +11,12 @@
 // The model is data: the float32 table that PlanarChain.model_table() packs from the model spec
 // (evoxmi/problems/neuroevolution/reinforcement_learning/planar.py, the CPU oracle) arrives by
 // value in the kernel-argument segment, so every parameter is a wave-uniform scalar load and the
-// launch captures into a hipGraph with no device copy of the table.  Only the tree shape is
-// compile-time: the kernel is instantiated per parent list (TOPO_PAR), every loop over bodies and
-// degrees of freedom is fully unrolled, and no register array is indexed by a run-time value.
+// launch captures into a hipGraph with no device copy of the table.  The tree shape, the root
+// constraint, the task kind and what the actions drive are compile-time: the kernel is instantiated
+// per combination (VARIANTS), every loop over bodies and degrees of freedom is fully unrolled, and
+// no register array is indexed by a run-time value.  A locked root coordinate keeps its initial
+// value, has velocity 0 and drops out of the mass matrix, the right-hand side and the LDLᵀ
+// elimination as a structural zero; with a fully locked root the system is the hinges alone.
 //
 // Physics per sub-step, lane-uniform float32 (PlanarChain._substep): q ← q + dt·u; kinematics down
 // the tree relative to the root point; per-body external wrenches (gravity, cap contacts, fluid
@@ -35,18 +39,45 @@
 namespace {
 
 constexpr int HDR = 24, BODY = 16, HINGE = 10, MAXB = 8, TABLE = HDR + MAXB * (BODY + HINGE);
-enum { H_NB, H_SKIP, H_SUB, H_DT, H_G, H_KC, H_CC, H_MU, H_EPS, H_LIN, H_ANG, H_CN, H_CT, H_CW, H_CLIP, H_HEALTHY, H_CTRL, H_ZLO, H_ZHI, H_PITCH };
+enum { H_NB, H_SKIP, H_SUB, H_DT, H_G, H_KC, H_CC, H_MU, H_EPS, H_LIN, H_ANG, H_CN, H_CT, H_CW, H_CLIP, H_HEALTHY, H_CTRL, H_ZLO, H_ZHI, H_PITCH,
+       H_LOCK, H_KIND, H_TIPX, H_TIPGOAL };  // the last four are 0 for a free root and the run task
 enum { B_PAR, B_AX, B_AZ, B_CX, B_CZ, B_M, B_I, B_CAP0, B_CAP1 = B_CAP0 + 4 };  // cap: x, z, radius, contact
-enum { J_GEAR, J_ARM, J_DAMP, J_STIFF, J_REST, J_LO, J_HI, J_LIMK };
+enum { J_GEAR, J_ARM, J_DAMP, J_STIFF, J_REST, J_LO, J_HI, J_LIMK, J_INIT, J_VELCOST };  // hinge row 0: the root slider's gear, lo, hi, limit_k
+enum { K_RUN, K_BALANCE, K_BALANCE_TIP, K_REACH };
 
 struct PlanarModel {
   float v[TABLE];
 };
 
-// tree shapes: chain of 3 (swimmer), chain of 4 (hopper), torso + two chains of 3 (walker2d, halfcheetah)
-constexpr int NTOPO = 3;
-constexpr int TOPO_NB[NTOPO] = {3, 4, 7};
-constexpr int TOPO_PAR[NTOPO][MAXB] = {{-1, 0, 1, 0, 0, 0, 0, 0}, {-1, 0, 1, 2, 0, 0, 0, 0}, {-1, 0, 1, 2, 0, 4, 5, 0}};
+// tree shapes: chain of 3 (swimmer, inverted_double_pendulum, reacher), chain of 4 (hopper), torso + two chains of 3
+// (walker2d, halfcheetah), chain of 2 (inverted_pendulum)
+constexpr int NTOPO = 4;
+constexpr int TOPO_NB[NTOPO] = {3, 4, 7, 2};
+constexpr int TOPO_PAR[NTOPO][MAXB] = {{-1, 0, 1, 0, 0, 0, 0, 0}, {-1, 0, 1, 2, 0, 0, 0, 0}, {-1, 0, 1, 2, 0, 4, 5, 0}, {-1, 0, 0, 0, 0, 0, 0, 0}};
+
+// what the kernel is instantiated for: tree shape, mask of locked root coordinates (1 x, 2 z, 4 θ), task kind, and what
+// the actions drive (the root slider first, then every hinge or none: a passive hinge reads no action)
+struct Variant {
+  int topo, lock, kind;
+  bool root_act, hinge_act;
+};
+constexpr int NVARIANT = 6;
+constexpr Variant VARIANTS[NVARIANT] = {{0, 0, K_RUN, false, true},        {1, 0, K_RUN, false, true},         {2, 0, K_RUN, false, true},
+                                        {3, 6, K_BALANCE, true, false},   {0, 6, K_BALANCE_TIP, true, false}, {0, 7, K_REACH, false, true}};
+// observations of a variant before obs_skip (run: q ++ u of the whole model; the others are built from free coordinates)
+constexpr int variant_obs(int v) {
+  const int nb = TOPO_NB[VARIANTS[v].topo], nj = nb - 1;
+  int nfr = 0;
+  for (int i = 0; i < 3; ++i) nfr += !((VARIANTS[v].lock >> i) & 1);
+  switch (VARIANTS[v].kind) {
+    case K_RUN: return 2 * (nb + 2);
+    case K_BALANCE: return 2 * (nfr + nj);
+    case K_BALANCE_TIP: return nfr + 2 * nj + nfr + nj;
+    default: return 3 * nj + 5;  // cos, sin, target (2), velocities, tip − target (2), 0
+  }
+}
+constexpr int variant_act(int v) { return (VARIANTS[v].root_act ? 1 : 0) + (VARIANTS[v].hinge_act ? TOPO_NB[VARIANTS[v].topo] - 1 : 0); }
+constexpr int variant_aux(int v) { return VARIANTS[v].kind == K_REACH ? 2 : 0; }
 
 constexpr bool anc(int T, int b, int k) {  // body k is b or an ancestor of b
   while (b >= 0) {
@@ -84,9 +115,16 @@ __device__ __forceinline__ float pair_sum(float v) {
 
 // T: the tree shape this lane integrates.  SPLIT: the lane's chain is one of two hanging on the same root
 // (the other one lives in lane ^ 1); whatever a chain adds to the root is summed over the lane pair.
-template <int T, bool SPLIT>
+// LOCK: mask of locked root coordinates.  SLIDER: root x is driven along a slider with a limit spring.
+// TIP: keep the world position of the last body's far end cap (tipx, tipz) at the pose of the last sub-step.
+template <int T, bool SPLIT, int LOCK = 0, bool SLIDER = false, bool TIP = false>
 struct Chain {
   static constexpr int NB = TOPO_NB[T], ND = NB + 2;
+  // π_θ is advanced with the linear momenta, so a free θ needs free translations
+  static_assert(LOCK == 0 || LOCK == 6 || LOCK == 7, "root constraints: free, x only, or fully locked");
+  static_assert(!(SPLIT && LOCK), "the two-chain root is free");
+  static __device__ __forceinline__ constexpr bool fr(int i) { return i >= 3 || !((LOCK >> i) & 1); }  // coordinate i is free
+  float tipx, tipz;
   float q[ND], u[ND], pi[ND];  // π: P_x, P_z, angular momentum about the root point, hinge momenta
   float Bp[NB][BODY - 1], Jp[NB][J_LIMK + 1];  // this lane's body and hinge rows of the model table
   bool cap_on[NB][2];  // wave-uniform: the cap is a contact sphere in some lane (SPLIT: in either chain)
@@ -127,7 +165,7 @@ struct Chain {
     float ca[NB], sa[NB], hx[NB], hz[NB], rx[NB], rz[NB];
     float w[NB], vhx[NB], vhz[NB], vcx[NB], vcz[NB];
   };
-  __device__ __forceinline__ void pose(const PlanarModel& m, Pose& k) const {
+  __device__ __forceinline__ void pose(const PlanarModel& m, Pose& k) {
     float al[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
@@ -154,6 +192,11 @@ struct Chain {
       k.rz[b] = k.sa[b] * B[B_CX] + k.ca[b] * B[B_CZ];
       k.vcx[b] = k.vhx[b] - k.w[b] * k.rz[b];
       k.vcz[b] = k.vhz[b] + k.w[b] * k.rx[b];
+    }
+    if (TIP) {
+      const float* C = Bp[NB - 1] + B_CAP1;
+      tipx = q[0] + k.hx[NB - 1] + (k.ca[NB - 1] * C[0] - k.sa[NB - 1] * C[1]);
+      tipz = q[1] + k.hz[NB - 1] + (k.sa[NB - 1] * C[0] + k.ca[NB - 1] * C[1]);
     }
   }
 
@@ -202,10 +245,14 @@ struct Chain {
     if (momenta_from_u) {  // π = M u (episode start)
 #pragma unroll
       for (int i = 0; i < ND; ++i) {
+        if (!fr(i)) {
+          pi[i] = 0.f;  // never read
+          continue;
+        }
         float acc = 0.f, chain = 0.f;  // chain: what this lane's hinges add to a root momentum
 #pragma unroll
         for (int j = 0; j < ND; ++j)
-          if (rel(i, j) && !(i < 2 && j < 2 && i != j)) {
+          if (rel(i, j) && fr(j) && !(i < 2 && j < 2 && i != j)) {
             const float t = (j <= i ? A[i][j] : A[j][i]) * u[j];
             if (SPLIT && i < 3 && j >= 3)
               chain += t;
@@ -222,6 +269,7 @@ struct Chain {
     float D[3][3] = {}, dr[3] = {};  // SPLIT: what eliminating this lane's hinges takes from the root's 3 × 3 system
 #pragma unroll
     for (int l = ND - 1; l >= 0; --l) {
+      if (!fr(l)) continue;
       if (SPLIT && l == 2) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
@@ -233,7 +281,7 @@ struct Chain {
       inv[l] = __builtin_amdgcn_rcpf(A[l][l]);
 #pragma unroll
       for (int i = l - 1; i >= 0; --i) {
-        if (!rel(i, l)) continue;
+        if (!rel(i, l) || !fr(i)) continue;
         const float f = A[l][i] * inv[l];
         if (SPLIT && l >= 3 && i < 3) {
 #pragma unroll
@@ -242,7 +290,7 @@ struct Chain {
         } else {
 #pragma unroll
           for (int j = 0; j <= i; ++j)
-            if (rel(j, l)) A[i][j] -= f * A[l][j];
+            if (rel(j, l) && fr(j)) A[i][j] -= f * A[l][j];
           r[i] -= f * r[l];
         }
         A[l][i] = f;
@@ -250,19 +298,22 @@ struct Chain {
     }
 #pragma unroll
     for (int l = 0; l < ND; ++l) {
+      if (!fr(l)) continue;
       float acc = r[l] * inv[l];
 #pragma unroll
       for (int i = 0; i < l; ++i)
-        if (rel(i, l)) acc -= A[l][i] * u[i];
+        if (rel(i, l) && fr(i)) acc -= A[l][i] * u[i];
       u[l] = acc;
     }
   }
 
-  __device__ __forceinline__ void substep(const PlanarModel& m, const float* tau) {
+  // tau: the hinge torques; froot: the force of the root slider's actuator (SLIDER)
+  __device__ __forceinline__ void substep(const PlanarModel& m, const float* tau, float froot) {
     const float* H = m.v;
     const float dt = H[H_DT];
 #pragma unroll
-    for (int i = 0; i < ND; ++i) q[i] += dt * u[i];
+    for (int i = 0; i < ND; ++i)
+      if (fr(i)) q[i] += dt * u[i];
     Pose k;
     pose(m, k);
     // external wrench per body about the root point, and the bodies' linear momenta
@@ -308,6 +359,7 @@ struct Chain {
         fx -= H[H_LIN] * u[0];
         fz -= H[H_LIN] * u[1];
         n -= H[H_ANG] * u[2];
+        if (SLIDER) fx += froot + Jp[0][J_LIMK] * (fmaxf(Jp[0][J_LO] - q[0], 0.f) - fmaxf(q[0] - Jp[0][J_HI], 0.f));
       }
       Fx[b] = fx;
       Fz[b] = fz;
@@ -340,29 +392,32 @@ struct Chain {
       const float dT = k.vhz[j] * Px[j] - k.vhx[j] * Pz[j];
       pi[2 + j] += dt * (tj + Q + dT);
     }
-    pi[2] += dt * (Nr[0] - (u[0] * pi[1] - u[1] * pi[0]));
-    pi[0] += dt * Fx[0];
-    pi[1] += dt * Fz[0];
+    if (fr(2)) pi[2] += dt * (Nr[0] - (u[0] * pi[1] - u[1] * pi[0]));
+    if (fr(0)) pi[0] += dt * Fx[0];
+    if (fr(1)) pi[1] += dt * Fz[0];
     solve(m, k, false);
   }
 };
 
-template <int T>
+template <int V>
 __global__ void __launch_bounds__(256) planar_rollout_kernel(const float* __restrict__ W, int64_t P, int N, int h1, int h2,
                                                              const PlanarModel m, const float* __restrict__ init, int cap,
                                                              float* __restrict__ ret, int* __restrict__ steps_out, int waves_per_block) {
+  constexpr int T = VARIANTS[V].topo, LOCK = VARIANTS[V].lock, KIND = VARIANTS[V].kind;
+  constexpr bool ROOT_ACT = VARIANTS[V].root_act, HINGE_ACT = VARIANTS[V].hinge_act;
   // T == 2 (a root with two chains of 3): every lane integrates the chain of 4 made of the root and its own chain
   constexpr bool SPLIT = T == 2;
-  using C = Chain<SPLIT ? 1 : T, SPLIT>;
-  constexpr int NBT = TOPO_NB[T], NDT = NBT + 2, NA = NBT - 1;  // the whole model
-  constexpr int ND = C::ND, NJ = C::NB - 1;                      // this lane's part
+  using C = Chain<SPLIT ? 1 : T, SPLIT, LOCK, ROOT_ACT, KIND == K_BALANCE_TIP || KIND == K_REACH>;
+  constexpr int NBT = TOPO_NB[T], NDT = NBT + 2, NA = variant_act(V);  // the whole model
+  constexpr int ND = C::ND, NJ = C::NB - 1;                            // this lane's part
+  constexpr int NOV = variant_obs(V);                                  // observation entries before obs_skip
   extern __shared__ float smem[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int ind = blockIdx.x * waves_per_block + wv;
   const bool w1reg = w1_in_registers(h1);
   const float* H = m.v;
   const int skip = (int)H[H_SKIP], nsub = (int)H[H_SUB];
-  const int no = 2 * NDT - skip;
+  const int no = NOV - skip;
   // per-wave LDS: weights (P, without W1 when it lives in registers) | 32 spare | act1 (h1) | act2 (h2) | actions (8)
   const int64_t w0 = w1reg ? (int64_t)no * h1 : 0, Pl = P - w0;
   const int64_t per = Pl + 32 + h1 + h2 + 8;
@@ -373,13 +428,13 @@ __global__ void __launch_bounds__(256) planar_rollout_kernel(const float* __rest
   if (ind >= N) return;
   const float* wg = W + (int64_t)ind * P;
   for (int64_t i = lane; i < Pl; i += 64) wl[i] = wg[w0 + i];
-  // W1 in registers: lane j keeps columns j and j + 64, rows aligned with q ++ u (zero for the skipped entries)
-  float w1r[2][2 * NDT];
+  // W1 in registers: lane j keeps columns j and j + 64, one row per observation entry (zero for the skipped entries)
+  float w1r[2][NOV];
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
     const int j = lane + 64 * c;
 #pragma unroll
-    for (int i = 0; i < 2 * NDT; ++i) w1r[c][i] = (w1reg && j < h1 && i >= skip) ? wg[(int64_t)(i - skip) * h1 + j] : 0.f;
+    for (int i = 0; i < NOV; ++i) w1r[c][i] = (w1reg && j < h1 && i >= skip) ? wg[(int64_t)(i - skip) * h1 + j] : 0.f;
   }
   const float* W1 = wl;  // (not read when W1 is in registers)
   const float* B1 = wl + ((int64_t)no * h1 - w0);
@@ -395,7 +450,12 @@ __global__ void __launch_bounds__(256) planar_rollout_kernel(const float* __rest
   for (int i = 0; i < ND; ++i) {
     const int g = i < 3 ? i : i + joff;
     s.q[i] = init[g];
-    s.u[i] = init[NDT + g];
+    s.u[i] = C::fr(i) ? init[NDT + g] : 0.f;  // a locked coordinate is at rest
+  }
+  float tgx = 0.f, tgz = 0.f;  // the reach task's target: the two words after q ++ u
+  if (KIND == K_REACH) {
+    tgx = init[2 * NDT];
+    tgz = init[2 * NDT + 1];
   }
   {
     typename C::Pose k;
@@ -408,18 +468,51 @@ __global__ void __launch_bounds__(256) planar_rollout_kernel(const float* __rest
   int t = 0;
   __builtin_amdgcn_wave_barrier();
   for (; t < cap; ++t) {
-    float o[2 * NDT];  // the whole model's q ++ u, lane-uniform
+    float o[NOV];  // the observation entries, lane-uniform
+    if constexpr (KIND == K_RUN) {  // the whole model's q ++ u
 #pragma unroll
-    for (int i = 0; i < ND; ++i) {
-      const float ui = fminf(fmaxf(s.u[i], -clip), clip);
-      if (SPLIT && i >= 3) {  // hinges: the first chain's from lane 0, the second's from lane 1
-        o[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.q[i]), 0));
-        o[i + NJ] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.q[i]), 1));
-        o[NDT + i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ui), 0));
-        o[NDT + i + NJ] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ui), 1));
-      } else {
-        o[i] = s.q[i];
-        o[NDT + i] = ui;
+      for (int i = 0; i < ND; ++i) {
+        const float ui = fminf(fmaxf(s.u[i], -clip), clip);
+        if (SPLIT && i >= 3) {  // hinges: the first chain's from lane 0, the second's from lane 1
+          o[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.q[i]), 0));
+          o[i + NJ] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.q[i]), 1));
+          o[NDT + i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ui), 0));
+          o[NDT + i + NJ] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ui), 1));
+        } else {
+          o[i] = s.q[i];
+          o[NDT + i] = ui;
+        }
+      }
+    } else {
+      int n = 0;  // a constant after unrolling
+      if constexpr (KIND == K_BALANCE || KIND == K_BALANCE_TIP) {  // free root coordinates, hinges, free velocities
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+          if (C::fr(i)) o[n++] = s.q[i];
+        if constexpr (KIND == K_BALANCE) {
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) o[n++] = s.q[3 + j];
+        } else {
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) o[n++] = __sinf(s.q[3 + j]);
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) o[n++] = __cosf(s.q[3 + j]);
+        }
+#pragma unroll
+        for (int i = 0; i < ND; ++i)
+          if (C::fr(i)) o[n++] = s.u[i];
+      } else {  // reach: cos φ, sin φ, target, φ̇, tip − target, 0 (the out-of-plane component of Brax's layout)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) o[n++] = __cosf(s.q[3 + j]);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) o[n++] = __sinf(s.q[3 + j]);
+        o[n++] = tgx;
+        o[n++] = tgz;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) o[n++] = s.u[3 + j];
+        o[n++] = s.tipx - tgx;
+        o[n++] = s.tipz - tgz;
+        o[n++] = 0.f;
       }
     }
     if (w1reg) {
@@ -429,7 +522,7 @@ __global__ void __launch_bounds__(256) planar_rollout_kernel(const float* __rest
         if (j < h1) {
           float acc = B1[j];
 #pragma unroll
-          for (int i = 0; i < 2 * NDT; ++i) acc = fmaf(o[i], w1r[c][i], acc);
+          for (int i = 0; i < NOV; ++i) acc = fmaf(o[i], w1r[c][i], acc);
           a1[j] = tanhf(acc);
         }
       }
@@ -437,7 +530,7 @@ __global__ void __launch_bounds__(256) planar_rollout_kernel(const float* __rest
       for (int j = lane; j < h1; j += 64) {
         float acc = B1[j];
 #pragma unroll
-        for (int i = 0; i < 2 * NDT; ++i)
+        for (int i = 0; i < NOV; ++i)
           if (i >= skip) acc = fmaf(o[i], W1[(i - skip) * h1 + j], acc);
         a1[j] = tanhf(acc);
       }
@@ -456,24 +549,45 @@ __global__ void __launch_bounds__(256) planar_rollout_kernel(const float* __rest
       a3[lane] = tanhf(acc);
     }
     __builtin_amdgcn_wave_barrier();
-    float tau[NJ], csum = 0.f;
+    float tau[NJ], csum = 0.f, froot = 0.f;
 #pragma unroll
     for (int j = 0; j < NA; ++j) {
       const float a = fminf(fmaxf(a3[j], -1.f), 1.f);
       csum += a * a;
     }
+    // action columns: the root slider's first, then the hinges in body order; a passive hinge reads none
+    if (ROOT_ACT) froot = s.Jp[0][J_GEAR] * fminf(fmaxf(a3[0], -1.f), 1.f);
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) tau[j] = s.Jp[j + 1][J_GEAR] * fminf(fmaxf(a3[joff + j], -1.f), 1.f);
+    for (int j = 0; j < NJ; ++j) tau[j] = HINGE_ACT ? s.Jp[j + 1][J_GEAR] * fminf(fmaxf(a3[(ROOT_ACT ? 1 : 0) + joff + j], -1.f), 1.f) : 0.f;
     __builtin_amdgcn_wave_barrier();  // a1..a3 are rewritten next step
     const float x0 = s.q[0];
-    for (int kk = 0; kk < nsub; ++kk) s.substep(m, tau);
+    for (int kk = 0; kk < nsub; ++kk) s.substep(m, tau, froot);
     float nf = 0.f;
 #pragma unroll
     for (int i = 0; i < ND; ++i) nf += s.q[i] * 0.f + s.u[i] * 0.f;  // NaN unless every entry is finite
     if (SPLIT) nf = pair_sum(nf);
-    const bool healthy = (s.q[1] > H[H_ZLO]) && (s.q[1] < H[H_ZHI]) && (fabsf(s.q[2]) < H[H_PITCH]) && (nf == 0.f);
+    bool healthy = nf == 0.f;
+    float reward;
+    if constexpr (KIND == K_RUN) {
+      healthy = (s.q[1] > H[H_ZLO]) && (s.q[1] < H[H_ZHI]) && (fabsf(s.q[2]) < H[H_PITCH]) && healthy;
+      reward = (s.q[0] - x0) * idtc + H[H_HEALTHY] - H[H_CTRL] * csum;
+    } else if constexpr (KIND == K_BALANCE) {  // the first pole's absolute angle
+      healthy = (fabsf(s.q[2] + s.q[3]) < H[H_PITCH]) && healthy;
+      reward = H[H_HEALTHY] - H[H_CTRL] * csum;
+    } else if constexpr (KIND == K_BALANCE_TIP) {
+      healthy = (s.tipz > H[H_ZLO]) && healthy;
+      float vel = 0.f;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) vel += m.v[HDR + MAXB * BODY + (j + 1) * HINGE + J_VELCOST] * (s.u[3 + j] * s.u[3 + j]);
+      const float dz = s.tipz - H[H_TIPGOAL];
+      reward = H[H_HEALTHY] - (H[H_TIPX] * (s.tipx * s.tipx) + dz * dz) - vel;
+    } else {
+      const float dx = s.tipx - tgx, dz = s.tipz - tgz;
+      healthy = healthy && ((tgx + tgz) * 0.f == 0.f);
+      reward = -sqrtf(dx * dx + dz * dz) - H[H_CTRL] * csum;
+    }
     if (!healthy) break;  // sticky done: the terminating step earns nothing
-    total += (s.q[0] - x0) * idtc + H[H_HEALTHY] - H[H_CTRL] * csum;
+    total += reward;
   }
   if (lane == 0) {
     ret[ind] = total;
@@ -481,44 +595,71 @@ __global__ void __launch_bounds__(256) planar_rollout_kernel(const float* __rest
   }
 }
 
-int topology_of(const float* model) {
+// what the actions of the table's model drive, against a variant's pattern
+bool actuation_matches(const float* model, int v) {
+  const int nb = TOPO_NB[VARIANTS[v].topo];
+  const float* J0 = model + HDR + MAXB * BODY;
+  const bool slider = J0[J_GEAR] != 0.f || J0[J_LIMK] != 0.f;
+  if (VARIANTS[v].root_act ? J0[J_GEAR] == 0.f : slider) return false;
+  for (int j = 1; j < nb; ++j)
+    if ((J0[j * HINGE + J_GEAR] != 0.f) != VARIANTS[v].hinge_act) return false;
+  return true;
+}
+
+// the instantiation for the table's tree shape, locked root coordinates, task kind and actuation, or -1
+int variant_of(const float* model) {
   const int nb = (int)model[H_NB];
-  for (int t = 0; t < NTOPO; ++t) {
-    if (TOPO_NB[t] != nb) continue;
-    bool same = true;
+  for (int v = 0; v < NVARIANT; ++v) {
+    const int t = VARIANTS[v].topo;
+    if (TOPO_NB[t] != nb || model[H_LOCK] != (float)VARIANTS[v].lock || model[H_KIND] != (float)VARIANTS[v].kind) continue;
+    bool same = actuation_matches(model, v);
     for (int b = 0; b < nb; ++b) same = same && (int)model[HDR + b * BODY + B_PAR] == TOPO_PAR[t][b];
-    if (same) return t;
+    if (same) return v;
   }
   return -1;
 }
 
-template <int T>
+template <int V>
 void launch(const float* W, int64_t P, int N, int h1, int h2, const PlanarModel& m, const float* init, int cap, float* ret, int* steps,
             hipStream_t s) {
-  const int nb = (int)m.v[H_NB], no = 2 * (nb + 2) - (int)m.v[H_SKIP];
+  const int no = variant_obs(V) - (int)m.v[H_SKIP];
   const int64_t per = (P - (w1_in_registers(h1) ? (int64_t)no * h1 : 0) + 32 + h1 + h2 + 8) * 4;
   int waves = 4;
   while (waves > 1 && per * waves > 160 * 1024) --waves;
   const int blocks = (N + waves - 1) / waves;
-  (void)hipFuncSetAttribute((const void*)planar_rollout_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(per * waves));
-  planar_rollout_kernel<T><<<blocks, 64 * waves, per * waves, s>>>(W, P, N, h1, h2, m, init, cap, ret, steps, waves);
+  (void)hipFuncSetAttribute((const void*)planar_rollout_kernel<V>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(per * waves));
+  planar_rollout_kernel<V><<<blocks, 64 * waves, per * waves, s>>>(W, P, N, h1, h2, m, init, cap, ret, steps, waves);
 }
 
 }  // namespace
 
 int evx_planar_table_words() { return TABLE; }
 
-// 0 when the kernel is instantiated for the table's tree shape, else -1 (the table is host memory)
-int evx_planar_supported(const float* model) { return topology_of(model) >= 0 ? 0 : -1; }
+// 0 when the kernel is instantiated for the table's combination of tree shape, root constraint, task kind and
+// actuation, else -1 (the table is host memory)
+int evx_planar_supported(const float* model) { return variant_of(model) >= 0 ? 0 : -1; }
+
+// observations (after obs_skip), actions and auxiliary state words of a supported table's model; -1 when it is not supported
+int evx_planar_dims(const float* model, int* no, int* na, int* naux) {
+  const int v = variant_of(model);
+  if (v < 0) return -1;
+  *no = variant_obs(v) - (int)model[H_SKIP];
+  *na = variant_act(v);
+  *naux = variant_aux(v);
+  return 0;
+}
 
 void evx_planar_rollout(const float* W, int64_t P, int N, int h1, int h2, const float* model, const float* init, int cap, float* ret,
                         int* steps, hipStream_t s) {
   PlanarModel m;
   for (int i = 0; i < TABLE; ++i) m.v[i] = model[i];
-  switch (topology_of(model)) {
+  switch (variant_of(model)) {
     case 0: launch<0>(W, P, N, h1, h2, m, init, cap, ret, steps, s); break;
     case 1: launch<1>(W, P, N, h1, h2, m, init, cap, ret, steps, s); break;
     case 2: launch<2>(W, P, N, h1, h2, m, init, cap, ret, steps, s); break;
+    case 3: launch<3>(W, P, N, h1, h2, m, init, cap, ret, steps, s); break;
+    case 4: launch<4>(W, P, N, h1, h2, m, init, cap, ret, steps, s); break;
+    case 5: launch<5>(W, P, N, h1, h2, m, init, cap, ret, steps, s); break;
     default: break;  // rejected by the binding (evx_planar_supported)
   }
 }

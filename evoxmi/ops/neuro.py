@@ -37,10 +37,14 @@ def planar_rollout(flat_weights: torch.Tensor, h1: int, h2: int, model: torch.Te
     articulated-tree model.  ``model`` is the float32 table of ``PlanarChain.model_table()`` (kept
     in host memory: it is passed to the kernel by value, so the launch captures into a hipGraph);
     the MLP obs-h1-h2-act (tanh) weights are rows of ``flat_weights`` in the layout [W1 (obs×h1),
-    b1, W2 (h1×h2), b2, W3 (h2×act), b3]; every individual starts from ``init_state`` (2·nd,) =
-    q ++ u.  Raises for a model or policy outside the kernel's caps (≤ 8 bodies, ≤ 10 degrees of
-    freedom, ≤ 32 observations, ≤ 8 actions, hidden ≤ 512, ``planar_lds_bytes`` ≤ ``PLANAR_LDS_LIMIT``, a
-    supported tree shape)."""
+    b1, W2 (h1×h2), b2, W3 (h2×act), b3]; every individual starts from ``init_state`` (2·nd + n_aux,) =
+    q ++ u ++ aux (the reach task's target; nothing for the other kinds).  The observation, action and
+    auxiliary sizes follow from the table.  Raises for a model or policy outside the kernel's caps (≤ 8
+    bodies, ≤ 10 degrees of freedom, ≤ 32 observations, ≤ 8 actions, hidden ≤ 512, ``planar_lds_bytes`` ≤
+    ``PLANAR_LDS_LIMIT``) or outside the six instantiated combinations of tree shape, root constraint and task
+    kind: chains of 3 or 4 bodies or a root with two chains of 3 with a free root and the run task (every hinge
+    driven); chain of 2, x-only root, balance and chain of 3, x-only root, balance_tip (the slider driven, the
+    hinges passive); chain of 3, locked root, reach (both hinges driven)."""
     return _ext.ops().planar_rollout(flat_weights.to(torch.float32).contiguous(), int(h1), int(h2),
                                      model.to(device="cpu", dtype=torch.float32).contiguous(),
                                      init_state.to(device=flat_weights.device, dtype=torch.float32).contiguous(), int(cap))

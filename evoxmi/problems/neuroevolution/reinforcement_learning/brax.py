@@ -11,8 +11,9 @@ Execution paths:
 * **fused** (``"ant"`` + :class:`~evoxmi.models.MLPPolicy` 27-h1-h2-8 tanh, on a GPU):
   one persistent HIP kernel runs whole episodes with each individual's weights held
   in LDS (``ops.neuro.ant_rollout``);
-* **fused, planar** (``"hopper"``, ``"walker2d"``, ``"halfcheetah"``, ``"swimmer"`` or any
-  :class:`~.planar.PlanarChain` within the kernel's caps + a 3-layer tanh/tanh
+* **fused, planar** (``"hopper"``, ``"walker2d"``, ``"halfcheetah"``, ``"swimmer"``, ``"inverted_pendulum"``,
+  ``"inverted_double_pendulum"``, ``"reacher"`` or any :class:`~.planar.PlanarChain` within the kernel's caps
+  and of one of its six combinations of tree shape, root constraint and task kind + a 3-layer tanh/tanh
   :class:`~evoxmi.models.MLPPolicy` of matching sizes with hidden ≤ 512 whose weights fit one wave's
   share of LDS (hidden up to about 190), on a GPU): the
   table-driven persistent kernel ``ops.neuro.planar_rollout``;

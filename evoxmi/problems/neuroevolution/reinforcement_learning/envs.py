@@ -27,6 +27,8 @@ that keeps each individual's MLP weights in LDS for the whole episode.
   Reference behaviour: ``src/evox/problems/neuroevolution/reinforcement_learning/brax.py:51-73``.
 * ``hopper``, ``walker2d``, ``halfcheetah``, ``swimmer`` — the planar Brax-style tasks on the
   table-driven articulated-tree engine of :mod:`.planar` (fused rollout: ``ops.neuro.planar_rollout``).
+* ``inverted_pendulum``, ``inverted_double_pendulum``, ``reacher`` — the same engine with a constrained root
+  (a cart on a rail, an arm on a locked base), a driven root slider, passive hinges and their own task forms.
 """
 from __future__ import annotations
 
@@ -51,7 +53,9 @@ def get_environment(env_name: str, **kwargs):
     key = env_name.lower().replace("-v1", "").replace("-v0", "").replace("-v4", "").replace("-v5", "")
     aliases = {"cartpole": "cartpole", "pendulum": "pendulum", "mountaincarcontinuous": "mountain_car_continuous",
                "mountain_car_continuous": "mountain_car_continuous", "ant": "ant", "hopper": "hopper", "walker2d": "walker2d",
-               "halfcheetah": "halfcheetah", "swimmer": "swimmer"}
+               "halfcheetah": "halfcheetah", "swimmer": "swimmer", "inverted_pendulum": "inverted_pendulum",
+               "invertedpendulum": "inverted_pendulum", "inverted_double_pendulum": "inverted_double_pendulum",
+               "inverteddoublependulum": "inverted_double_pendulum", "reacher": "reacher"}
     if key not in aliases:
         raise ValueError(f"unknown environment {env_name!r}; native environments: {sorted(ENVS)}")
     return ENVS[aliases[key]](**kwargs)
@@ -432,4 +436,4 @@ class Ant:
         return s, self.obs(s), reward, ~healthy
 
 
-from . import planar  # noqa: E402,F401  (registers hopper, walker2d, halfcheetah, swimmer)
+from . import planar  # noqa: E402,F401  (registers hopper, walker2d, halfcheetah, swimmer, the pendulums and the reacher)

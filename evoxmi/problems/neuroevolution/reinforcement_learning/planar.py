@@ -1,4 +1,5 @@
-"""Planar articulated-tree engine and the four planar Brax-style locomotion tasks.
+"""Planar articulated-tree engine and the planar Brax-style tasks: four that run (hopper, walker2d,
+halfcheetah, swimmer), two that balance (inverted_pendulum, inverted_double_pendulum) and the reacher.
 
 ``PlanarChain`` integrates a tree of rigid links that moves in one plane (vertical for
 hopper / walker2d / halfcheetah, horizontal for the swimmer) from a declarative model spec,
@@ -36,6 +37,25 @@ One sub-step is symplectic Euler in momentum form, the scheme of ``envs.Ant._sub
    momentum of the hinge's subtree (planar angular velocities do not depend on ``q``);
 3. ``u = M(q)⁻¹ π``, ``M = Σ_b J_bᵀ diag(m_b, m_b, I_b) J_b + diag(armature)``, by a Cholesky
    solve of the dense ``nd × nd`` matrix.
+
+Constrained root, slider, passive hinges, task kinds (all optional; the defaults are the above)
+-------------------------------------------------------------------------------------------------
+``root_free=(fx, fz, fθ)`` locks root coordinates: a locked one keeps its ``root_init`` value exactly, has
+velocity exactly 0 and gets no reset noise.  The sub-step then advances the generalized momenta of the free
+coordinates ``F`` directly (``π_θ`` about the root point, ``∂T/∂φ_k`` in the same closed form) and solves the
+reduced system ``M[F, F] u_F = π_F``; the momentum rows of locked coordinates are never read.
+``root_gear=(gx, 0, 0)`` and ``root_slider=dict(lo, hi, limit_k)`` drive root x: its force is
+``gx·a − lin_damp·ẋ + limit_k·(clamp(lo − x, 0) − clamp(x − hi, 0))``.  A hinge with gear 0 is passive and takes no
+action: ``act_dim`` counts the non-zero gears, the slider's column first, then the hinges in body order.
+``task["kind"]`` is ``"run"`` (forward velocity, health on root height and pitch, observation ``q ++ u``),
+``"balance"`` (observation ``q_F ++ u_F``, reward ``healthy_reward − ctrl_cost·‖a‖²``, unhealthy when the first
+link's absolute angle reaches ``pitch_max``), ``"balance_tip"`` (observation free root coordinates, ``sin φ``,
+``cos φ``, ``u_F``; reward ``healthy_reward − (tip_x_cost·x_tip² + (z_tip − tip_goal)²) − Σ_j vel_cost_j·φ̇_j²``;
+unhealthy when ``z_tip ≤ z_lo``; the tip is the far end cap of the last body) or ``"reach"`` (two hinges;
+observation ``cos φ, sin φ, target, φ̇, tip − target, 0``; reward ``−‖tip − target‖ − ctrl_cost·‖a‖²``).  A
+non-finite state is unhealthy in every kind.  The state is ``q ++ u ++ aux`` with ``state_dim = 2·nd + n_aux``:
+``aux`` is the reach task's target (2 words, uniform in a disc of ``target_radius``, drawn at reset from
+``fold_in(key, 1)``) and empty otherwise; ``step`` carries it through unchanged.
 """
 from __future__ import annotations
 
@@ -57,8 +77,18 @@ TABLE_WORDS = TABLE_HEADER + MAX_BODIES * (TABLE_BODY + TABLE_HINGE)
 _HEADER_FIELDS = ("n_bodies", "obs_skip", "substeps", "dt", "gravity", "contact_k", "contact_c", "mu", "eps_v", "lin_damp", "ang_damp",
                   "fluid_cn", "fluid_ct", "fluid_cw", "vel_clip", "healthy_reward", "ctrl_cost", "z_lo", "z_hi", "pitch_max")
 _HINGE_FIELDS = ("gear", "armature", "damping", "stiffness", "rest", "lo", "hi", "limit_k", "init")
-# tree shapes the kernel is instantiated for (parent lists)
-FUSED_TOPOLOGIES = ((-1, 0, 1), (-1, 0, 1, 2), (-1, 0, 1, 2, 0, 4, 5))
+# words added for constrained roots and task kinds; every one is 0 for a free-root "run" model, so those tables are unchanged:
+# header 20 … 23, hinge row 0 (the root slider, at the hinge fields' own offsets) and word 9 of every hinge row (vel_cost)
+_HEADER_EXTRA = ("root_lock", "kind", "tip_x_cost", "tip_goal")
+_SLIDER_FIELDS = ("gear", "lo", "hi", "limit_k")
+VEL_COST_WORD = len(_HINGE_FIELDS)
+KINDS = ("run", "balance", "balance_tip", "reach")
+_TASK_DEFAULTS = dict(kind="run", obs_skip=0, vel_clip=0.0, healthy_reward=0.0, ctrl_cost=0.0, z_lo=-INF, z_hi=INF, pitch_max=INF,
+                      tip_x_cost=0.0, tip_goal=0.0, vel_cost=None, target_radius=0.0)
+# what the kernel is instantiated for: (parent list, mask of locked root coordinates (1 x, 2 z, 4 θ), task kind)
+FUSED_COMBINATIONS = (((-1, 0, 1), 0, "run"), ((-1, 0, 1, 2), 0, "run"), ((-1, 0, 1, 2, 0, 4, 5), 0, "run"),
+                      ((-1, 0), 6, "balance"), ((-1, 0, 1), 6, "balance_tip"), ((-1, 0, 1), 7, "reach"))
+FUSED_TOPOLOGIES = tuple(c[0] for c in FUSED_COMBINATIONS[:3])
 
 
 def capsule(parent, anchor, p0, p1, radius, mass, contact=(1, 1)):
@@ -138,7 +168,43 @@ def _swimmer():
                 root_init=(0.0, 0.0, 0.0), reset_noise=0.1, standing_band=None)
 
 
+def _no_ground():
+    return dict(contact_k=0.0, contact_c=0.0, mu=0.0, eps_v=0.05, ang_damp=0.0, fluid_cn=0.0, fluid_ct=0.0, fluid_cw=0.0, standing_band=None)
+
+
+def _cart():
+    return capsule(-1, (0, 0), (-0.1, 0), (0.1, 0), 0.1, 10.5, contact=(0, 0))
+
+
+def _inverted_pendulum():
+    pole = capsule(0, (0, 0), (0, 0), (0, 0.6), 0.049, 5.0, contact=(0, 0))
+    return dict(name="inverted_pendulum", bodies=(_cart(), pole), hinges=(hinge(0.0, -INF, INF, damping=0.05),),
+                gravity=9.81, dt=0.002, substeps=10, lin_damp=1.0, root_free=(1, 0, 0), root_gear=(100.0, 0.0, 0.0),
+                root_slider=dict(lo=-1.0, hi=1.0, limit_k=5000.0),
+                task=dict(kind="balance", healthy_reward=1.0, ctrl_cost=0.0, pitch_max=0.2),
+                root_init=(0.0, 0.0, 0.0), reset_noise=0.01, **_no_ground())
+
+
+def _inverted_double_pendulum():
+    poles = (capsule(0, (0, 0), (0, 0), (0, 0.6), 0.045, 4.2, contact=(0, 0)), capsule(1, (0, 0.6), (0, 0), (0, 0.6), 0.045, 4.2, contact=(0, 0)))
+    return dict(name="inverted_double_pendulum", bodies=(_cart(),) + poles, hinges=(hinge(0.0, -INF, INF, damping=0.05), hinge(0.0, -INF, INF, damping=0.05)),
+                gravity=9.81, dt=0.001, substeps=20, lin_damp=1.0, root_free=(1, 0, 0), root_gear=(500.0, 0.0, 0.0),
+                root_slider=dict(lo=-1.0, hi=1.0, limit_k=5000.0),
+                task=dict(kind="balance_tip", healthy_reward=10.0, tip_x_cost=0.01, tip_goal=2.0, vel_cost=(1e-3, 5e-3), z_lo=1.0),
+                root_init=(0.0, 0.0, 0.0), reset_noise=0.05, **_no_ground())
+
+
+def _reacher():
+    bodies = (capsule(-1, (0, 0), (-0.01, 0), (0.01, 0), 0.02, 1.0, contact=(0, 0)), capsule(0, (0, 0), (0, 0), (0.1, 0), 0.01, 0.0356, contact=(0, 0)),
+              capsule(1, (0.1, 0), (0, 0), (0.11, 0), 0.01, 0.0387, contact=(0, 0)))
+    hinges = (hinge(200.0, -INF, INF, armature=1.0, damping=1.0), hinge(200.0, -3.0, 3.0, armature=1.0, damping=1.0, limit_k=1000.0))
+    return dict(name="reacher", bodies=bodies, hinges=hinges, gravity=0.0, dt=0.01, substeps=2, lin_damp=0.0, root_free=(0, 0, 0),
+                task=dict(kind="reach", ctrl_cost=1.0, target_radius=0.2),
+                root_init=(0.0, 0.0, 0.0), reset_noise=0.1, **_no_ground())
+
+
 HOPPER, WALKER2D, HALFCHEETAH, SWIMMER = _hopper(), _walker2d(), _halfcheetah(), _swimmer()
+INVERTED_PENDULUM, INVERTED_DOUBLE_PENDULUM, REACHER = _inverted_pendulum(), _inverted_double_pendulum(), _reacher()
 
 
 def _rot(c, s, v):
@@ -170,29 +236,65 @@ class PlanarChain:
         self.parents = tuple(int(b["parent"]) for b in spec["bodies"])
         if self.parents[0] != -1 or any(not 0 <= p < i for i, p in enumerate(self.parents) if i > 0):
             raise ValueError("PlanarChain: body 0 is the root and every parent index precedes its child")
-        t = spec["task"]
+        t = self.task = dict(_TASK_DEFAULTS, **spec["task"])
+        self.kind = t["kind"]
+        if self.kind not in KINDS:
+            raise ValueError(f"PlanarChain: task kind {self.kind!r} is not one of {KINDS}")
         self.obs_skip = int(t["obs_skip"])
-        self.obs_dim = 2 * self.nd - self.obs_skip
-        self.act_dim = self.nj
-        self.state_dim = 2 * self.nd
+        self.root_free = tuple(bool(f) for f in spec.get("root_free", (1, 1, 1)))
+        self.root_lock = sum(1 << i for i, f in enumerate(self.root_free) if not f)
+        self.free = tuple(i for i in range(3) if self.root_free[i]) + tuple(range(3, self.nd))
+        self.n_free_root = len(self.free) - self.nj
+        self.root_gear = tuple(float(g) for g in spec.get("root_gear", (0.0, 0.0, 0.0)))
+        if self.root_gear[1] or self.root_gear[2] or (self.root_gear[0] and not self.root_free[0]):
+            raise ValueError("PlanarChain: only a free root x can be driven (root_gear = (gx, 0, 0))")
+        self.slider = spec.get("root_slider")
+        self.act_hinges = tuple(j for j, h in enumerate(spec["hinges"]) if h["gear"] != 0)
+        self.act_dim = (1 if self.root_gear[0] else 0) + len(self.act_hinges)
+        self.vel_cost = tuple(float(v) for v in (t["vel_cost"] or (0.0,) * self.nj))
+        if len(self.vel_cost) != self.nj:
+            raise ValueError("PlanarChain: one vel_cost per hinge")
+        if self.kind == "reach" and self.nj != 2:
+            raise ValueError("PlanarChain: the reach task is a two-hinge arm")
+        nf = len(self.free)
+        self.n_aux = 2 if self.kind == "reach" else 0
+        self.obs_dim = {"run": 2 * nf - self.obs_skip, "balance": 2 * nf, "balance_tip": self.n_free_root + 2 * self.nj + nf, "reach": 11}[self.kind]
+        self.state_dim = 2 * self.nd + self.n_aux
         self._consts = {}
 
     # -- caps of the fused kernel -------------------------------------------------------
+    def _fused_combination(self):
+        """The kernel is instantiated for this tree shape, root constraint, task kind and actuation: the slider driven
+        and every hinge passive for the two balance kinds, no slider and every hinge driven for the others."""
+        if (self.parents, self.root_lock, self.kind) not in FUSED_COMBINATIONS:
+            return False
+        slider = bool(self.root_gear[0]) or bool(self.slider and self.slider["limit_k"])
+        if self.kind in ("balance", "balance_tip"):
+            return bool(self.root_gear[0]) and not self.act_hinges and self.obs_skip == 0
+        return not slider and len(self.act_hinges) == self.nj and (self.kind == "run" or self.obs_skip == 0)
+
     def within_caps(self):
         return (self.nb <= MAX_BODIES and self.nd <= MAX_DOF and self.obs_dim <= MAX_OBS and self.act_dim <= MAX_ACT
-                and self.parents in FUSED_TOPOLOGIES)
+                and self._fused_combination())
 
     def model_table(self):
         """The float32 table (``TABLE_WORDS``) the fused kernel reads: header, 8 body rows, 8 hinge
-        rows (row ``j`` = the hinge of body ``j``; row 0 unused).  Raises for a model over the caps."""
+        rows (row ``j`` = the hinge of body ``j``; row 0 holds the root slider's gear, range and limit spring).
+        Raises for a model over the caps."""
         if self.nb > MAX_BODIES or self.nd > MAX_DOF or self.obs_dim > MAX_OBS or self.act_dim > MAX_ACT:
             raise ValueError(f"PlanarChain: model {self.spec.get('name')!r} exceeds the fused-kernel caps "
                              f"({MAX_BODIES} bodies, {MAX_DOF} DOF, {MAX_OBS} observations, {MAX_ACT} actions)")
-        s, t = self.spec, self.spec["task"]
+        s, t = self.spec, self.task
         tab = torch.zeros(TABLE_WORDS, dtype=torch.float64)
-        vals = dict(s, **t, n_bodies=self.nb)
-        for i, f in enumerate(_HEADER_FIELDS):
+        vals = {**s, **t, "n_bodies": self.nb, "root_lock": self.root_lock, "kind": KINDS.index(self.kind)}
+        for i, f in enumerate(_HEADER_FIELDS + _HEADER_EXTRA):
             tab[i] = float(vals[f])
+        ho = TABLE_HEADER + MAX_BODIES * TABLE_BODY
+        slider = dict(self.slider or dict(lo=0.0, hi=0.0, limit_k=0.0), gear=self.root_gear[0])
+        for f in _SLIDER_FIELDS:
+            tab[ho + _HINGE_FIELDS.index(f)] = float(slider[f])
+        for j, v in enumerate(self.vel_cost):
+            tab[ho + (j + 1) * TABLE_HINGE + VEL_COST_WORD] = v
         for b, body in enumerate(s["bodies"]):
             o = TABLE_HEADER + b * TABLE_BODY
             row = [body["parent"], *body["anchor"], *body["com"], body["mass"], body["inertia"], *body["caps"][0], *body["caps"][1]]
@@ -216,6 +318,21 @@ class PlanarChain:
             o = TABLE_HEADER + MAX_BODIES * TABLE_BODY + j * TABLE_HINGE
             hinges.append(dict(zip(_HINGE_FIELDS, tab[o:o + len(_HINGE_FIELDS)])))
         out["bodies"], out["hinges"] = tuple(bodies), tuple(hinges)
+        # what a constrained root or another task kind adds (absent for a free-root "run" model)
+        ho = TABLE_HEADER + MAX_BODIES * TABLE_BODY
+        extra = {f: tab[len(_HEADER_FIELDS) + i] for i, f in enumerate(_HEADER_EXTRA)}
+        slider = {f: tab[ho + _HINGE_FIELDS.index(f)] for f in _SLIDER_FIELDS}
+        vel_cost = tuple(tab[ho + j * TABLE_HINGE + VEL_COST_WORD] for j in range(1, nb))
+        if extra["root_lock"]:
+            out["root_free"] = tuple(0 if int(extra["root_lock"]) >> i & 1 else 1 for i in range(3))
+        if extra["kind"]:
+            out["kind"] = KINDS[int(extra["kind"])]
+        if out.get("kind") == "balance_tip":
+            out.update(tip_x_cost=extra["tip_x_cost"], tip_goal=extra["tip_goal"], vel_cost=vel_cost)
+        if slider["gear"]:
+            out["root_gear"] = (slider["gear"], 0.0, 0.0)
+        if slider["limit_k"]:
+            out["root_slider"] = dict(lo=slider["lo"], hi=slider["hi"], limit_k=slider["limit_k"])
         return out
 
     # -- constants of the model as tensors ----------------------------------------------
@@ -248,6 +365,11 @@ class PlanarChain:
         for f in _HINGE_FIELDS:
             c[f] = torch.tensor([h[f] for h in s["hinges"]], **o)
         c["arm_diag"] = torch.diag(torch.cat([torch.zeros(3, **o), c["armature"]]))
+        c["free"] = torch.tensor(self.free, device=ref.device)
+        c["free_mask"] = torch.zeros(self.nd, **o).index_fill_(0, c["free"], 1.0)
+        c["act_hinges"] = torch.tensor(self.act_hinges, dtype=torch.long, device=ref.device)
+        c["vel_cost"] = torch.tensor(self.vel_cost, **o)
+        c["tip_pt"] = torch.tensor(s["bodies"][-1]["caps"][1][:2], **o)
         self._consts[key] = c
         return c
 
@@ -314,19 +436,18 @@ class PlanarChain:
 
     def momentum(self, s):
         """Total linear momentum (N, 2) and angular momentum about the world origin (N,)."""
-        q, u = s[:, :self.nd], s[:, self.nd:]
+        q, u = s[:, :self.nd], s[:, self.nd:2 * self.nd]
         pi = self.momenta(q, u)
         return pi[:, :2], pi[:, 2] + q[:, 0] * pi[:, 1] - q[:, 1] * pi[:, 0]
 
     def initial_momenta(self, s):
         P, L = self.momentum(s)
-        return P, L, self.momenta(s[:, :self.nd], s[:, self.nd:])[:, 3:]
+        return P, L, self.momenta(s[:, :self.nd], s[:, self.nd:2 * self.nd])[:, 3:]
 
     # -- dynamics -----------------------------------------------------------------------
-    def _substep(self, q, u, mom, tau):
+    def _substep(self, q, u, mom, tau, root_force=0.0):
         c, S = self._c(q), self.spec
         dt, nb = S["dt"], self.nb
-        P, L, pj = mom
         q = q + dt * u
         k = self._kin(q)
         Jc = self._jac(k, k["cm"], c["body_ids"], q)
@@ -355,6 +476,21 @@ class PlanarChain:
         lim = torch.clamp(c["lo"] - phi, min=0) - torch.clamp(phi - c["hi"], min=0)
         tj = tau - c["damping"] * phid - c["stiffness"] * (phi - c["rest"]) + c["limit_k"] * lim
         dT = self._dTdq_from(k, Jc, u, q)
+        if self.root_gear[0] or self.slider:  # the driven slider of root x, with its limit spring
+            fx = self.root_gear[0] * root_force
+            if self.slider:
+                sl = self.slider
+                fx = fx + sl["limit_k"] * (torch.clamp(sl["lo"] - q[:, 0], min=0) - torch.clamp(q[:, 0] - sl["hi"], min=0))
+            Q = torch.cat([(Q[:, 0] + fx)[:, None], Q[:, 1:]], 1)
+        if self.root_lock:
+            # generalized momenta of the free coordinates, advanced directly (π_θ about the root point); a locked
+            # coordinate's row takes a constraint force that is never computed, and the row is never read
+            pi = mom + dt * (torch.cat([Q[:, :3], Q[:, 3:] + tj], 1) + dT)
+            F = c["free"]
+            M = self._mass_matrix(k, Jc, q)[:, F][:, :, F]
+            uf = torch.cholesky_solve(pi[:, F, None], torch.linalg.cholesky_ex(M).L)[..., 0]
+            return q, torch.zeros_like(u).index_copy_(1, F, uf), pi
+        P, L, pj = mom
         P = P + dt * Q[:, :2]
         L = L + dt * (Q[:, 2] + q[:, 0] * Q[:, 1] - q[:, 1] * Q[:, 0])
         pj = pj + dt * (tj + Q[:, 3:] + dT[:, 3:])
@@ -363,47 +499,95 @@ class PlanarChain:
         u = torch.cholesky_solve(pi[..., None], torch.linalg.cholesky_ex(M).L)[..., 0]  # a non-finite state stays non-finite (unhealthy)
         return q, u, (P, L, pj)
 
+    def tip(self, q):
+        """World position (N, 2) of the far end cap of the last body."""
+        c, k = self._c(q), self._kin(q)
+        return k["hp"][:, -1] + _rot(k["ca"][:, -1], k["sa"][:, -1], c["tip_pt"])
+
     def healthy(self, s):
-        t = self.spec["task"]
+        t = self.task
+        finite = torch.isfinite(s).all(1)
+        if self.kind == "balance":
+            return ((s[:, 2] + s[:, 3]).abs() < t["pitch_max"]) & finite
+        if self.kind == "balance_tip":
+            return (self.tip(s[:, :self.nd])[:, 1] > t["z_lo"]) & finite
+        if self.kind == "reach":
+            return finite
         z, th = s[:, 1], s[:, 2]
-        return (z > t["z_lo"]) & (z < t["z_hi"]) & (th.abs() < t["pitch_max"]) & torch.isfinite(s).all(1)
+        return (z > t["z_lo"]) & (z < t["z_hi"]) & (th.abs() < t["pitch_max"]) & finite
 
     def obs(self, s):
-        u = s[:, self.nd:]
-        clip = self.spec["task"]["vel_clip"]
-        if clip:
-            u = torch.clamp(u, -clip, clip)
-        return torch.cat([s[:, self.obs_skip:self.nd], u], 1)
+        nd = self.nd
+        q, u = s[:, :nd], s[:, nd:2 * nd]
+        if self.kind == "run":
+            clip = self.task["vel_clip"]
+            if clip:
+                u = torch.clamp(u, -clip, clip)
+            if not self.root_lock:
+                return torch.cat([q[:, self.obs_skip:], u], 1)
+        F = self._c(s)["free"]
+        if self.kind in ("run", "balance"):
+            return torch.cat([q[:, F][:, self.obs_skip:], u[:, F]], 1)
+        phi = q[:, 3:]
+        if self.kind == "balance_tip":
+            return torch.cat([q[:, F[:self.n_free_root]], torch.sin(phi), torch.cos(phi), u[:, F]], 1)
+        target = s[:, 2 * nd:]
+        return torch.cat([torch.cos(phi), torch.sin(phi), target, u[:, 3:], self.tip(q) - target, torch.zeros_like(q[:, :1])], 1)
 
     def reset(self, key, n):
         S = self.spec
         k1, k2 = rnd.split(key)
         q = torch.tensor(list(S["root_init"]) + [h["init"] for h in S["hinges"]], dtype=torch.float32)
-        q = q + S["reset_noise"] * (rnd.uniform(k1, (self.nd,)).to(torch.float32) * 2 - 1)
+        dq = S["reset_noise"] * (rnd.uniform(k1, (self.nd,)).to(torch.float32) * 2 - 1)
         u = S["reset_noise"] * rnd.normal(k2, (self.nd,)).to(torch.float32)
-        s = torch.cat([q, u]).expand(n, 2 * self.nd).clone()
+        if self.root_lock:  # a locked coordinate starts at root_init exactly, at rest
+            free = self._c(q)["free_mask"]
+            dq, u = dq * free, u * free
+        parts = [q + dq, u]
+        if self.kind == "reach":  # the target: uniform in a disc, from a key of its own
+            r, ang = rnd.uniform(rnd.fold_in(key, 1), (2,)).to(torch.float32)
+            rad = self.task["target_radius"] * torch.sqrt(r)
+            parts.append(torch.stack([rad * torch.cos(2 * math.pi * ang), rad * torch.sin(2 * math.pi * ang)]))
+        s = torch.cat(parts).expand(n, self.state_dim).clone()
         return s, self.obs(s)
 
     def step(self, s, action):
-        S, t = self.spec, self.spec["task"]
+        S, t = self.spec, self.task
         c = self._c(s)
+        nd = self.nd
         a = torch.clamp(action.to(s.dtype), -1.0, 1.0)
-        tau = c["gear"] * a
-        q, u = s[:, :self.nd], s[:, self.nd:]
+        root_force = 0.0
+        if not self.root_gear[0] and len(self.act_hinges) == self.nj:  # every hinge is driven and nothing else
+            tau = c["gear"] * a
+        else:  # the root slider's column first, then the driven hinges in body order; a passive hinge takes none
+            na_root = 1 if self.root_gear[0] else 0
+            if na_root:
+                root_force = a[:, 0]
+            tau = torch.zeros_like(s[:, :self.nj]).index_copy_(1, c["act_hinges"], c["gear"][c["act_hinges"]] * a[:, na_root:])
+        q, u, aux = s[:, :nd], s[:, nd:2 * nd], s[:, 2 * nd:]
         x0 = q[:, 0]
-        mom = self.initial_momenta(s)
+        mom = self.momenta(q, u) if self.root_lock else self.initial_momenta(s)
         for _ in range(S["substeps"]):
-            q, u, mom = self._substep(q, u, mom, tau)
-        s = torch.cat([q, u], 1)
+            q, u, mom = self._substep(q, u, mom, tau, root_force)
+        s = torch.cat([q, u, aux], 1) if self.n_aux else torch.cat([q, u], 1)
         healthy = self.healthy(s)
-        reward = (q[:, 0] - x0) / (S["dt"] * S["substeps"]) + t["healthy_reward"] - t["ctrl_cost"] * (a * a).sum(1)
+        ctrl = t["ctrl_cost"] * (a * a).sum(1)
+        if self.kind == "run":
+            reward = (q[:, 0] - x0) / (S["dt"] * S["substeps"]) + t["healthy_reward"] - ctrl
+        elif self.kind == "balance":
+            reward = t["healthy_reward"] - ctrl
+        elif self.kind == "balance_tip":
+            tip = self.tip(q)
+            reward = t["healthy_reward"] - (t["tip_x_cost"] * tip[:, 0] ** 2 + (tip[:, 1] - t["tip_goal"]) ** 2) - (c["vel_cost"] * u[:, 3:] ** 2).sum(1)
+        else:
+            reward = -(self.tip(q) - aux).norm(dim=1) - ctrl
         reward = torch.where(healthy, reward, torch.zeros_like(reward))
         return s, self.obs(s), reward, ~healthy
 
     # -- rendering ----------------------------------------------------------------------
     def render(self, state, width=320, height=240, span=None):
-        """``(H, W, 3) uint8`` side view of one state ``(2·nd,)``: links as thick segments, the ground
-        line at ``z = 0`` (planar-vertical models), the camera centred on the root."""
+        """``(H, W, 3) uint8`` side view of one state ``(state_dim,)``: links as thick segments, the ground
+        line at ``z = 0`` (models with contacts only), the reach task's target as a dot, the camera centred on the root."""
         s = state.detach().to("cpu", torch.float64).reshape(1, -1)
         c, k = self._c(s), self._kin(s[:, :self.nd])
         X = (k["hp"][:, c["cap_body"]] + _rot(k["ca"][:, c["cap_body"]], k["sa"][:, c["cap_body"]], c["cap_pt"]))[0].numpy()
@@ -424,6 +608,9 @@ class PlanarChain:
             tpar = np.clip(((gx - p0[0]) * d[0] + (gz - p0[1]) * d[1]) / max(float(d @ d), 1e-12), 0, 1)
             dist = np.hypot(gx - (p0[0] + tpar * d[0]), gz - (p0[1] + tpar * d[1]))
             img[dist <= rad] = (200, 60, 40) if b == 0 else (40, 90 + 20 * (b % 3), 200)
+        if self.kind == "reach":  # the target
+            tx, tz = (float(v) for v in s[0, 2 * self.nd:])
+            img[np.hypot(gx - tx, gz - tz) <= max(0.009, 2.0 * span / width)] = (40, 160, 60)
         return torch.from_numpy(img)
 
 
@@ -479,3 +666,47 @@ class Swimmer(PlanarChain):
     Observation ``q[2:] ++ u``; reward = forward velocity − 1e-4‖a‖²; never ends (non-finite only)."""
 
     SPEC = SWIMMER
+
+
+@register("inverted_pendulum")
+class InvertedPendulum(PlanarChain):
+    """Brax-style InvertedPendulum (4 observations / 1 action), not bit-compatible with Brax / MuJoCo.
+
+    A cart (capsule 0.2 long, radius 0.1, mass 10.5) on a rail: the root is free in x only (z and θ locked at 0).
+    The pole (0.6 long, radius 0.049, mass 5) stands upright at φ = 0 on a passive hinge (gear 0, damping 0.05, no
+    armature, no range).  The one action drives the slider with gear 100; slider damping 1, range ±1 with a limit
+    spring of 5000 N/m.  Gravity 9.81, no contacts; 10 sub-steps of 2 ms per 20 ms control step (the explicit step
+    gains energy once the pole whirls; that lies behind the termination rule).  Observation ``(x, φ, ẋ, φ̇)``;
+    reward = 1 while healthy; ends when |φ| ≥ 0.2 or the state is non-finite.  Reset noise 0.01."""
+
+    SPEC = INVERTED_PENDULUM
+
+
+@register("inverted_double_pendulum")
+class InvertedDoublePendulum(PlanarChain):
+    """Brax-style InvertedDoublePendulum (8 / 1), not bit-compatible with Brax / MuJoCo.
+
+    The inverted pendulum's cart (mass 10.5, root free in x only) with two poles of 0.6 (radius 0.045, mass 4.2
+    each) on passive hinges (damping 0.05, no armature, no range).  Slider gear 500, damping 1, range ±1 with a
+    limit spring of 5000 N/m.  Gravity 9.81, no contacts; 20 sub-steps of 1 ms per 20 ms control step: released
+    from 0.01 rad the explicit step multiplies the energy by 200 within 75 control steps at 10 ms and only drifts
+    at 1 ms, and the tip is below 1 long before the poles whirl.  Observation ``(x, sin φ₁, sin φ₂, cos φ₁,
+    cos φ₂, ẋ, φ̇₁, φ̇₂)``; reward = 10 − (0.01·x_tip² + (z_tip − 2)²) − 1e-3·φ̇₁² − 5e-3·φ̇₂², the tip being the
+    far end of the second pole; ends when z_tip ≤ 1 or the state is non-finite.  Reset noise 0.05."""
+
+    SPEC = INVERTED_DOUBLE_PENDULUM
+
+
+@register("reacher")
+class Reacher(PlanarChain):
+    """Brax-style Reacher (11 / 2), not bit-compatible with Brax / MuJoCo.
+
+    A two-link arm in a horizontal plane (gravity 0, no contacts) on a fully locked root (a base of mass 1 that
+    never moves).  Links 0.1 and 0.11 (radius 0.01, masses 0.0356 / 0.0387); both hinges gear 200, armature 1,
+    damping 1; the second has range ±3 with a limit spring of 1000 N·m/rad.  The link inertia of about 1e-4 is
+    dominated by the armature (with armature 0 the step diverges).  2 sub-steps of 10 ms per 20 ms control step.
+    The target is drawn at reset, uniform in a disc of radius 0.2, and rides in the state's two last words.
+    Observation ``cos φ (2), sin φ (2), target (2), φ̇ (2), tip − target (2), 0``; reward = −‖tip − target‖ −
+    ‖a‖²; never ends (non-finite only).  Reset noise 0.1."""
+
+    SPEC = REACHER

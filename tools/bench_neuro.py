@@ -1,5 +1,5 @@
 """OpenES + Brax-style Ant throughput (north-star config 4: pop 8192, MLP 27-64-64-8), or one of the
-planar tasks with --env {hopper,walker2d,halfcheetah,swimmer}.
+planar tasks with --env {hopper,walker2d,halfcheetah,swimmer,inverted_pendulum,inverted_double_pendulum,reacher}.
 
 python tools/bench_neuro.py [--env ant] [--pop 8192] [--cap 1000] [--gens 5]
 torchrun --nproc-per-node N tools/bench_neuro.py ...   (population sharded over N GPUs:
@@ -27,7 +27,7 @@ def main():
     ap.add_argument("--pop", type=int, default=8192)
     ap.add_argument("--gpus", type=int, default=1, help="ranks (one per GPU); spawned here unless torchrun started them")
     ap.add_argument("--cap", type=int, default=1000)
-    ap.add_argument("--env", default="ant", choices=["ant", "hopper", "walker2d", "halfcheetah", "swimmer"])
+    ap.add_argument("--env", default="ant", choices=["ant", "hopper", "walker2d", "halfcheetah", "swimmer", "inverted_pendulum", "inverted_double_pendulum", "reacher"])
     ap.add_argument("--gens", type=int, default=5)
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--wscale", type=float, default=0.1)
