@@ -1211,8 +1211,13 @@ void moead_halo_replace(at::Tensor& obj, const at::Tensor& off_obj, const at::Te
     CHECK_DEV(*t); CHECK_CONTIG(*t);
     TORCH_CHECK(t->scalar_type() == at::kInt, "moead_halo_replace: int32 index tensors");
   }
-  const int64_t M = obj.size(1);
-  TORCH_CHECK(M <= 16 && off_obj.size(1) == M && win_h.numel() >= slots.numel(), "moead_halo_replace: shapes");
+  TORCH_CHECK(obj.dim() == 2 && off_obj.dim() == 2 && W.dim() == 2, "moead_halo_replace: obj, off_obj and W must be 2-d");
+  const int64_t N = obj.size(0), M = obj.size(1);
+  TORCH_CHECK(M >= 1 && M <= 16 && W.size(0) == N && W.size(1) == M && off_obj.size(1) == M && z.numel() == M && zmax.numel() == M &&
+                  win_h.numel() >= slots.numel(),
+              "moead_halo_replace: shapes");
+  TORCH_CHECK(rowptr.numel() == N + 1 && func >= 0 && func <= 4, "moead_halo_replace: rowptr must be (N+1,), func 0..4");
+  c10::DeviceGuard g(obj.device());
   evx_moead_halo_replace(obj.data_ptr<float>(), off_obj.data_ptr<float>(), W.data_ptr<float>(), z.data_ptr<float>(), zmax.data_ptr<float>(),
                          rowptr.data_ptr<int>(), owner.data_ptr<int>(), slots.data_ptr<int>(), (int)slots.numel(), (int)M, (int)func,
                          win_h.data_ptr<int>(), cur_stream());
@@ -1230,6 +1235,14 @@ void moead_halo_gather(at::Tensor& pop, const at::Tensor& slots, const at::Tenso
     fp = first->data_ptr<int>();
     nf = (int)first->numel();
   }
+  for (const at::Tensor* t : std::initializer_list<const at::Tensor*>{&slots, &win_h}) {
+    CHECK_DEV(*t); CHECK_CONTIG(*t);
+    TORCH_CHECK(t->scalar_type() == at::kInt, "moead_halo_gather: slots and win_h must be int32");
+  }
+  TORCH_CHECK(pop.dim() == 2 && win_h.numel() >= slots.numel() && peer.is_contiguous() && starts.is_contiguous(), "moead_halo_gather: shapes");
+  // one grid row (grid.y) per halo slot
+  TORCH_CHECK(slots.numel() <= 65535, "moead_halo_gather: at most 65535 halo slots, got ", slots.numel());
+  c10::DeviceGuard g(pop.device());
   evx_moead_halo_gather(pop.data_ptr<float>(), slots.data_ptr<int>(), win_h.data_ptr<int>(), (int)slots.numel(), peer.data_ptr<int64_t>(),
                         starts.data_ptr<int>(), (int)peer.numel(), (int)pop.size(1), cur_stream(), fp, nf);
 }
@@ -1292,6 +1305,8 @@ at::Tensor moead_select_rows(const at::Tensor& pop, const at::Tensor& off, const
   for (auto* t : {&pop, &off}) { CHECK_DEV(*t); CHECK_F32(*t); CHECK_CONTIG(*t); }
   CHECK_DEV(win); TORCH_CHECK(win.scalar_type() == at::kInt && win.numel() == pop.size(0), "win must be int32 (N,)");
   TORCH_CHECK(off.size(1) == pop.size(1), "row width mismatch");
+  // one grid row (grid.y) per population row
+  TORCH_CHECK(pop.size(0) <= 65535, "moead_select_rows: at most 65535 rows, got ", pop.size(0));
   c10::DeviceGuard g(pop.device());
   auto out = at::empty_like(pop);
   if (pop.numel() > 0)
@@ -1306,6 +1321,7 @@ void moead_select_rows_(at::Tensor& pop, const at::Tensor& off, const at::Tensor
   TORCH_CHECK(win.is_cuda() && win.scalar_type() == at::kInt && win.is_contiguous() && win.numel() == pop.size(0), "moead_select_rows_: win int32[N]");
   TORCH_CHECK(off.dim() == 2 && off.size(1) == pop.size(1), "moead_select_rows_: off (rows, d)");
   TORCH_CHECK(pop.data_ptr() != off.data_ptr(), "moead_select_rows_: off must not alias pop");
+  TORCH_CHECK(pop.size(0) <= 65535, "moead_select_rows_: at most 65535 rows, got ", pop.size(0));
   c10::DeviceGuard g(pop.device());
   if (pop.size(0) > 0 && pop.size(1) > 0)
     evx_moead_select_rows_inplace(pop.data_ptr<float>(), off.data_ptr<float>(), win.data_ptr<int>(), (int)pop.size(0), (int)pop.size(1),

@@ -38,12 +38,16 @@ __device__ __forceinline__ float agg(int func, const float* f, const float* w, c
     }
     return d1 + 5.f * sqrtf(d2);
   }
+  // fmaxf drops a NaN operand; a row with a NaN term aggregates to NaN (the CPU oracle's amax)
   float g = -INFINITY;
+  bool bad = false;
   for (int k = 0; k < M; ++k) {
     const float a = fabsf(f[k] - z[k]);
-    g = fmaxf(g, func == 3 ? a / w[k] : a * w[k]);  // 3: modified Tchebycheff, 0: Tchebycheff
+    const float v = func == 3 ? a / w[k] : a * w[k];  // 3: modified Tchebycheff, 0: Tchebycheff
+    bad |= v != v;
+    g = fmaxf(g, v);
   }
-  return g;
+  return bad ? NAN : g;
 }
 
 __global__ void __launch_bounds__(64) moead_scan_kernel(float* __restrict__ objs, const float* __restrict__ off_objs,
@@ -58,8 +62,8 @@ __global__ void __launch_bounds__(64) moead_scan_kernel(float* __restrict__ objs
   for (int i = 0; i < R; ++i) {
     float fo[MAXM];
     for (int k = 0; k < M; ++k) fo[k] = off_objs[(int64_t)i * M + k];
-    if (update_z)
-      for (int k = 0; k < M; ++k) z[k] = fminf(z[k], fo[k]);
+    if (update_z)  // as torch.minimum: a NaN propagates and stays (fminf alone drops it)
+      for (int k = 0; k < M; ++k) z[k] = (z[k] != z[k] || fo[k] != fo[k]) ? NAN : fminf(z[k], fo[k]);
     bool pred = false;
     int slot = 0;
     if (lane < T) {

@@ -52,16 +52,21 @@ __device__ __forceinline__ float agg(int func, const float* f, const float* w, c
     }
     return d1 + 5.f * sqrtf(d2);
   }
+  // fmaxf drops a NaN operand; the aggregate of a row with a NaN term is NaN (as amax in the
+  // torch path and the sequential oracle), so such a row neither takes a slot nor loses one:
+  // one flag per aggregate, not a NaN-aware max per term
   float g = -INFINITY;
+  bool bad = false;
   for (int k = 0; k < M; ++k) {
     const float a = fabsf(f[k] - z[k]);
     float v;
     if (func == 3) v = a / w[k];
     else if (func == 4) v = a / (zmax[k] - z[k]) * w[k];
     else v = a * w[k];
+    bad |= v != v;
     g = fmaxf(g, v);
   }
-  return g;
+  return bad ? NAN : g;
 }
 
 __device__ __forceinline__ void min2_merge(uint64_t& a1, uint64_t& a2, uint64_t b1, uint64_t b2) {

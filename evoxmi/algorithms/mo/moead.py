@@ -72,6 +72,9 @@ def moead_replace(pop_obj, off_obj, w, z, z_max, agg, rev):
     n = pop_obj.shape[0]
     f_old = agg(pop_obj, w, z, z_max)
     f_new = agg(off_obj[rev_owner], w[rev_slot], z, z_max)
+    # the scan's ``f_old > f_new`` is false for a NaN aggregate on either side: such an offspring never takes a
+    # slot (and must not poison the segment minimum for the others), such an occupant stays
+    f_new = torch.where(torch.isnan(f_new), torch.full_like(f_new, float("inf")), f_new)
     segmin, first = first_argmin_segments(f_new, rev_slot, n)
     better = segmin < f_old
     has = first < f_new.shape[0]

@@ -98,7 +98,8 @@ def moead_halo_gather(pop, slots, win_h, peer, starts, first=None):
 
 def moead_replace(pop_obj, off_obj, w, z, z_max, rowptr, owner, func):
     """Winner offspring per slot (or −1) and the new objective matrix — the exact parallel
-    form of the reference's sequential replacement scan (see algorithms/mo/moead.py)."""
+    form of the reference's sequential replacement scan (see algorithms/mo/moead.py).  As in that
+    scan an offspring whose aggregate is NaN takes no slot and an occupant whose aggregate is NaN stays."""
     fid = MOEAD_FUNCS[func] if isinstance(func, str) else int(func)
     f32 = lambda t: t.to(torch.float32).contiguous()
     return _ext.ops().moead_replace(f32(pop_obj), f32(off_obj), f32(w), f32(z), f32(z_max), rowptr, owner, fid)
