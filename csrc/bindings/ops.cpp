@@ -1643,6 +1643,57 @@ std::vector<at::Tensor> rvea_select(const at::Tensor& f, const c10::optional<at:
   return {next_ind, empty, arg, apd, gamma};
 }
 
+// bi (n, 2) float32, then pr and cd (n,) float64 of bige_select.hip: BiGE's bi-goal estimate of the masked rows of fit (n, m);
+// r is one float32 device word
+std::vector<at::Tensor> bige_estimate(const at::Tensor& fit, const at::Tensor& mask, const at::Tensor& r) {
+  CHECK_DEV(fit); CHECK_F32(fit); CHECK_CONTIG(fit); CHECK_DEV(mask); CHECK_CONTIG(mask); CHECK_DEV(r); CHECK_F32(r);
+  TORCH_CHECK(fit.dim() == 2, "bige_estimate: fit float32 (n, m)");
+  const int64_t n = fit.size(0), m = fit.size(1);
+  TORCH_CHECK(mask.scalar_type() == at::kBool && mask.dim() == 1 && mask.numel() == n, "bige_estimate: mask bool (n,)");
+  TORCH_CHECK(r.numel() == 1, "bige_estimate: r is one float32 device word");
+  TORCH_CHECK(mask.device() == fit.device() && r.device() == fit.device(), "bige_estimate: one device");
+  TORCH_CHECK(n >= 1 && n <= 32768, "bige_estimate: 1 <= n <= 32768");
+  TORCH_CHECK(m >= 1 && m <= 16, "bige_estimate: 1 <= m <= 16");
+  c10::DeviceGuard g(fit.device());
+  auto f64 = fit.options().dtype(at::kDouble);
+  auto ext = at::empty({2, m}, fit.options());
+  auto x = at::empty({m, n}, f64);
+  auto prs = at::empty({n}, f64);
+  auto bi = at::empty({n, 2}, fit.options());
+  auto pr = at::empty({n}, f64);
+  auto cd = at::empty({n}, f64);
+  evx_bige_estimate(fit.data_ptr<float>(), mask.data_ptr<bool>(), r.data_ptr<float>(), (int)n, (int)m, ext.data_ptr<float>(),
+                    ext.data_ptr<float>() + m, x.data_ptr<double>(), prs.data_ptr<double>(), bi.data_ptr<float>(), pr.data_ptr<double>(),
+                    cd.data_ptr<double>(), cur_stream());
+  return {bi, pr, cd};
+}
+
+// t_rank (n,) float32, then cls (n,) int32 and val (n,) float64 of tdea_select.hip on rvea_select.hip's best cosine: the θ-rank of
+// the masked rows of obj (n, m) on the directions w (nw, m); theta is (nw,) float32
+std::vector<at::Tensor> tdea_theta_rank(const at::Tensor& obj, const at::Tensor& w, const at::Tensor& theta, const at::Tensor& mask) {
+  rvea_check("tdea_theta_rank", obj, c10::nullopt, w);
+  CHECK_DEV(theta); CHECK_F32(theta); CHECK_CONTIG(theta); CHECK_DEV(mask); CHECK_CONTIG(mask);
+  const int64_t n = obj.size(0), nw = w.size(0), m = obj.size(1);
+  TORCH_CHECK(theta.dim() == 1 && theta.numel() == nw, "tdea_theta_rank: theta float32 (nw,)");
+  TORCH_CHECK(mask.scalar_type() == at::kBool && mask.dim() == 1 && mask.numel() == n, "tdea_theta_rank: mask bool (n,)");
+  TORCH_CHECK(theta.device() == obj.device() && mask.device() == obj.device(), "tdea_theta_rank: one device");
+  c10::DeviceGuard g(obj.device());
+  auto f64 = obj.options().dtype(at::kDouble);
+  auto bn = at::empty({m, nw}, f64);
+  auto best = at::empty({n}, f64);
+  auto arg = at::empty({n}, obj.options().dtype(at::kInt));
+  auto cls = at::empty({n}, obj.options().dtype(at::kInt));
+  auto val = at::empty({n}, f64);
+  auto t_rank = at::empty({n}, obj.options());
+  hipStream_t s = cur_stream();
+  evx_rvea_prepare(w.data_ptr<float>(), (int)nw, (int)m, bn.data_ptr<double>(), nullptr, nullptr, 0, s);
+  evx_rvea_cos_best(obj.data_ptr<float>(), nullptr, 0, 0.0, bn.data_ptr<double>(), (int)n, (int)nw, (int)m, 0, 0, 0, nullptr, nullptr,
+                    best.data_ptr<double>(), arg.data_ptr<int>(), nullptr, nullptr, s);
+  evx_tdea_theta_rank(obj.data_ptr<float>(), best.data_ptr<double>(), arg.data_ptr<int>(), theta.data_ptr<float>(), mask.data_ptr<bool>(),
+                      (int)n, (int)m, (int)nw, cls.data_ptr<int>(), val.data_ptr<double>(), t_rank.data_ptr<float>(), s);
+  return {t_rank, cls, val};
+}
+
 at::Tensor sra_rank(const at::Tensor& I1, const at::Tensor& I2, const at::Tensor& u, const at::Tensor& pc) {
   CHECK_DEV(I1); CHECK_F32(I1); CHECK_CONTIG(I1); CHECK_DEV(I2); CHECK_F32(I2); CHECK_CONTIG(I2);
   CHECK_DEV(u); CHECK_F32(u); CHECK_CONTIG(u); CHECK_DEV(pc); CHECK_F32(pc);
@@ -1976,6 +2027,8 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("knea_select(Tensor obj, Tensor rank, int N, Tensor r, Tensor t, float knee_rate) -> Tensor[]");
   m.def("rvea_cos_best(Tensor A, Tensor? shift, float? floor, Tensor B, bool clamp, bool self_zero) -> Tensor[]");
   m.def("rvea_select(Tensor f, Tensor? shift, float? floor, Tensor v, Tensor theta) -> Tensor[]");
+  m.def("bige_estimate(Tensor fit, Tensor mask, Tensor r) -> Tensor[]");
+  m.def("tdea_theta_rank(Tensor obj, Tensor w, Tensor theta, Tensor mask) -> Tensor[]");
   m.def("sra_rank(Tensor I1, Tensor I2, Tensor u, Tensor pc) -> Tensor");
   m.def("sra_indicators(Tensor obj) -> Tensor[]");
   m.def("ibea_fitness(Tensor obj_norm, float kappa) -> Tensor[]");
@@ -2080,6 +2133,8 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("knea_select", &knea_select);
   m.impl("rvea_cos_best", &rvea_cos_best);
   m.impl("rvea_select", &rvea_select);
+  m.impl("bige_estimate", &bige_estimate);
+  m.impl("tdea_theta_rank", &tdea_theta_rank);
   m.impl("sra_rank", &sra_rank);
   m.impl("sra_indicators", &sra_indicators);
   m.impl("ibea_fitness", &ibea_fitness);

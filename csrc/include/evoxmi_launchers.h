@@ -260,6 +260,17 @@ void evx_rvea_cos_best(const float* A, const float* shift, int has_floor, double
                        hipStream_t s);
 void evx_rvea_pick(const int* arg, const double* apd, int n, int nv, const uint64_t* key, int* pick, int64_t* next_ind, bool* empty,
                    hipStream_t s);
+// bige_select.hip: BiGE's bi-goal estimate (m ≤ 16; the contract is in evoxmi/ops/bige.py).  Three launches: the float32
+// column extremes of the masked rows into fmin, fmax (m each), the normalised rows into the float64 scratch x (m, n) and
+// their sums into prs (n), then bi (n, 2) float32 with its float64 parts pr and cd (n each); r is one float32 device
+// word
+void evx_bige_estimate(const float* f, const bool* mask, const float* r, int n, int m, float* fmin, float* fmax, double* x, double* prs,
+                       float* bi, double* pr, double* cd, hipStream_t s);
+// tdea_select.hip: θ-DEA's θ-ranking (the contract is in evoxmi/ops/tdea.py) from best and arg (n each) of
+// evx_rvea_cos_best, mode 0, of obj (n, m) against the nw directions: cls and val (n each), then t_rank (n,) float32, the
+// rank of every masked row among the masked rows of its cls, +inf outside the mask; theta is (nw,) float32
+void evx_tdea_theta_rank(const float* obj, const double* best, const int* arg, const float* theta, const bool* mask, int n, int m, int nw,
+                         int* cls, double* val, float* t_rank, hipStream_t s);
 // sra_select.hip: SRA's stochastic ranking (n ≤ evx_sra_rank_max_n(), pc one device word, rank (n,) best first)
 // and its two indicators in one pass (m ≤ evx_sra_indicators_max_m())
 int evx_sra_rank_max_n();

@@ -5,6 +5,9 @@ over a niche radius r = 1/N^{1/m}); mating and the last-front truncation use
 non-dominated sorting in that bi-goal space.  The reference's ``ask`` estimates the
 bi-goal values from the *decision vectors* (``bige.py:110``); the objectives are used
 here, as in the method.
+
+``ask`` and ``tell`` estimate with ``ops.bige.estimate``: ``bige_select.hip`` on a HIP device (float64, no (n, n)
+array), and ``estimate`` below, the dense float32 expression, on the CPU and above the kernels' caps.
 """
 from __future__ import annotations
 
@@ -12,6 +15,7 @@ import torch
 
 from ...operators import selection
 from ...operators.selection.non_dominate import non_dominated_sort
+from ...ops import bige as bige_ops
 from ...ops import random as rnd
 from .common import MOAlgorithm
 
@@ -42,7 +46,7 @@ class BiGE(MOAlgorithm):
 
     def ask(self, state):
         k0, k1, k2, k3 = rnd.split(state.key, 4)
-        bi = estimate(state.fitness, torch.ones(self.pop_size, dtype=torch.bool, device=state.fitness.device))
+        bi = bige_ops.estimate(state.fitness, torch.ones(self.pop_size, dtype=torch.bool, device=state.fitness.device))
         selected, _ = self.selection(k1, state.population, non_dominated_sort(bi).to(torch.float32))
         off = self._variation(k2, k3, selected)
         return off, state.update(next_generation=off, key=k0)
@@ -54,7 +58,7 @@ class BiGE(MOAlgorithm):
         order = torch.argsort(rank, stable=True)
         rank, pop, fit = rank[order], merged_pop[order], merged_fit[order]
         last = rank[self.pop_size]
-        bi_rank = non_dominated_sort(estimate(fit, rank == last))
+        bi_rank = non_dominated_sort(bige_ops.estimate(fit, rank == last))
         fin = torch.where(rank >= last, bi_rank, torch.full_like(bi_rank, -1))
         idx = torch.argsort(fin, stable=True)[: self.pop_size]
         return state.update(population=pop[idx], fitness=fit[idx])

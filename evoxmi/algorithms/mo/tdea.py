@@ -4,6 +4,9 @@ NSGA-III-style normalisation (ideal point, hyperplane through extreme points wit
 fallback to the worst point), clustering to the closest reference direction and
 θ-non-dominated sorting (rank inside each cluster by d1 + θ·d2, θ = 5, 10⁶ on the
 axes).  The per-cluster ranking loop of the reference is one (cluster, value) sort.
+
+``tell`` ranks with ``ops.tdea.theta_rank``: ``rvea_select.hip`` and ``tdea_select.hip`` on a HIP device (float64, no
+(n, nw) array), and ``theta_nd_sort`` below, the dense float32 expression, on the CPU and above the kernels' caps.
 """
 from __future__ import annotations
 
@@ -13,6 +16,7 @@ from ...core import State
 from ...operators.sampling import UniformSampling
 from ...operators.selection.non_dominate import lexsort, non_dominated_sort
 from ...ops import random as rnd
+from ...ops import tdea as tdea_ops
 from ...utils.common import cos_dist
 from .common import MOAlgorithm
 
@@ -81,6 +85,6 @@ class TDEA(MOAlgorithm):
         bad = (info != 0) | torch.isnan(a).any() | (a <= z).any()
         z_nad = torch.where(bad, obj.max(0).values, a)
         norm = (obj - z) / (z_nad - z)
-        t_rank = theta_nd_sort(norm, state.w, mask)
+        t_rank = tdea_ops.theta_rank(norm, state.w, mask)
         idx = lexsort([t_rank, rank.to(t_rank.dtype)])[:N]
         return state.update(population=pop[idx], fitness=obj[idx], z=z, z_nad=z_nad)

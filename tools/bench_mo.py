@@ -13,9 +13,11 @@
   rvea  : RVEA pop=4096 on DTLZ2 (m=3, d=500)              — 1×MI355X
   rveaa : RVEA* pop=4096 on DTLZ2 (m=3, d=500)             — 1×MI355X (3·pop rows against 2·pop vectors per generation)
   lmocso : LMOCSO pop=4096 on DTLZ2 (m=3, d=500)           — 1×MI355X
+  bige  : BiGE pop=4096 on DTLZ2 (m=3, d=500)              — 1×MI355X (two bi-goal estimates per generation)
+  tdea  : θ-DEA pop=4096 on DTLZ2 (m=3, d=500)             — 1×MI355X (the pop becomes the count of its reference directions)
   moead : MOEA/D pop=16384 on LSMOP1 (m=3, d=10000), Tchebycheff aggregation
 
-python tools/bench_mo.py --algo nsga2|nsga3|sra|ibea|spea2|bceibea|knea|m2m|rvea|rveaa|lmocso|moead [--gens 20] [--warmup 3] [--no-graph]
+python tools/bench_mo.py --algo nsga2|nsga3|sra|ibea|spea2|bceibea|knea|m2m|rvea|rveaa|lmocso|bige|tdea|moead [--gens 20] [--warmup 3] [--no-graph]
 torchrun --nproc-per-node 8 --master-addr 127.0.0.1 tools/bench_mo.py --algo moead
 
 Prints one JSON line (rank 0): generations/s and evaluations/s of full generations
@@ -39,15 +41,15 @@ import torch  # noqa: E402
 
 
 def build(args, dev):
-    from evoxmi.algorithms import BCEIBEA, IBEA, LMOCSO, MOEAD, MOEADM2M, NSGA2, NSGA3, RVEA, SPEA2, SRA, KnEA, RVEAa
+    from evoxmi.algorithms import BCEIBEA, IBEA, LMOCSO, MOEAD, MOEADM2M, NSGA2, NSGA3, RVEA, SPEA2, SRA, TDEA, BiGE, KnEA, RVEAa
     from evoxmi.problems.numerical import DTLZ2, LSMOP1
 
     m = 3
-    if args.algo in ("nsga2", "nsga3", "sra", "ibea", "spea2", "bceibea", "knea", "m2m", "rvea", "rveaa", "lmocso"):
+    if args.algo in ("nsga2", "nsga3", "sra", "ibea", "spea2", "bceibea", "knea", "m2m", "rvea", "rveaa", "lmocso", "bige", "tdea"):
         d = args.dim or 500
         lb, ub = torch.zeros(d, device=dev), torch.ones(d, device=dev)
         algos = {"nsga2": NSGA2, "nsga3": NSGA3, "sra": SRA, "ibea": IBEA, "spea2": SPEA2, "bceibea": BCEIBEA, "knea": KnEA,
-                 "m2m": MOEADM2M, "rvea": RVEA, "rveaa": RVEAa}
+                 "m2m": MOEADM2M, "rvea": RVEA, "rveaa": RVEAa, "bige": BiGE, "tdea": TDEA}
         if args.algo == "lmocso":  # its constructor takes n_objs first
             return LMOCSO(m, lb, ub, args.pop or 4096), DTLZ2(d=d, m=m)
         return algos[args.algo](lb, ub, m, args.pop or (4000 if args.algo == "m2m" else 4096)), DTLZ2(d=d, m=m)
@@ -62,7 +64,7 @@ def main():
     from evoxmi.workflows import StdWorkflow
 
     ap = argparse.ArgumentParser()
-    ap.add_argument("--algo", choices=["nsga2", "nsga3", "sra", "ibea", "spea2", "bceibea", "knea", "m2m", "rvea", "rveaa", "lmocso", "moead"], default="nsga2")
+    ap.add_argument("--algo", choices=["nsga2", "nsga3", "sra", "ibea", "spea2", "bceibea", "knea", "m2m", "rvea", "rveaa", "lmocso", "bige", "tdea", "moead"], default="nsga2")
     ap.add_argument("--gpus", type=int, default=1, help="ranks (one per GPU); spawned here unless torchrun started them")
     ap.add_argument("--pop", type=int, default=0)
     ap.add_argument("--dim", type=int, default=0)
