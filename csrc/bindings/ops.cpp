@@ -729,50 +729,6 @@ at::Tensor sbr_stats(const at::Tensor& A) {
   return out;
 }
 
-std::vector<at::Tensor> sbr_block(const at::Tensor& A, int64_t off, int64_t sweeps, const c10::optional<at::Tensor>& dbg) {
-  check_rowmajor(A, "A");
-  const int64_t n = A.size(0);
-  TORCH_CHECK(A.size(1) == n && n >= 2 && n <= 2048, "sbr_block: square A with 2 <= n <= 2048");
-  TORCH_CHECK(off == 0 || off == 32, "sbr_block: block offset must be 0 or 32");
-  c10::DeviceGuard g(A.device());
-  const int nb = evx_sbr_nblocks((int)n, (int)off);
-  auto perm = at::empty({n}, A.options().dtype(at::kInt));
-  auto Q = at::empty({nb, 64, 64}, A.options());
-  auto dq = at::empty({n}, A.options());
-  evx_sbr_block(A.data_ptr<float>(), (int)n, A.stride(0), (int)off, (int)sweeps, perm.data_ptr<int>(), Q.data_ptr<float>(),
-                dq.data_ptr<float>(), cur_stream(), dbg ? (long long*)dbg->data_ptr<int64_t>() : nullptr);
-  return {perm, Q, dq};
-}
-
-at::Tensor sbr_far(const at::Tensor& A, int64_t off, const at::Tensor& perm, const at::Tensor& Q, const at::Tensor& dq,
-                   const at::Tensor& stats, double thr_fac) {
-  check_rowmajor(A, "A");
-  const int64_t n = A.size(0);
-  const int nb = evx_sbr_nblocks((int)n, (int)off);
-  TORCH_CHECK(perm.is_cuda() && perm.scalar_type() == at::kInt && perm.numel() == n && perm.is_contiguous(), "perm int32[n]");
-  TORCH_CHECK(Q.is_cuda() && Q.scalar_type() == at::kFloat && Q.is_contiguous() && Q.numel() == (int64_t)nb * 4096, "Q [nb,64,64]");
-  TORCH_CHECK(dq.is_cuda() && dq.scalar_type() == at::kFloat && dq.numel() == n && dq.is_contiguous(), "dq float[n]");
-  TORCH_CHECK(stats.is_cuda() && stats.scalar_type() == at::kDouble && stats.numel() == 4, "stats double[4]");
-  c10::DeviceGuard g(A.device());
-  auto X = at::empty({n, n}, A.options());
-  evx_sbr_far(A.data_ptr<float>(), (int)n, A.stride(0), (int)off, perm.data_ptr<int>(), Q.data_ptr<float>(), dq.data_ptr<float>(),
-              stats.data_ptr<double>(), (float)thr_fac, X.data_ptr<float>(), n, cur_stream());
-  return X;
-}
-
-at::Tensor sbr_bq(const at::Tensor& B, int64_t off, const at::Tensor& perm, const at::Tensor& Q) {
-  check_rowmajor(B, "B");
-  const int64_t rows = B.size(0), n = B.size(1);
-  const int nb = evx_sbr_nblocks((int)n, (int)off);
-  TORCH_CHECK(perm.is_cuda() && perm.scalar_type() == at::kInt && perm.numel() == n && perm.is_contiguous(), "perm int32[n]");
-  TORCH_CHECK(Q.is_cuda() && Q.scalar_type() == at::kFloat && Q.is_contiguous() && Q.numel() == (int64_t)nb * 4096, "Q [nb,64,64]");
-  c10::DeviceGuard g(B.device());
-  auto Bq = at::empty({rows, n}, B.options());
-  evx_sbr_bq(B.data_ptr<float>(), (int)rows, (int)n, B.stride(0), (int)off, perm.data_ptr<int>(), Q.data_ptr<float>(),
-             Bq.data_ptr<float>(), n, cur_stream());
-  return Bq;
-}
-
 
 // 16-wide blocks in a shifted sorted order (eigh_sbr16.hip)
 std::vector<at::Tensor> sbr16_block(const at::Tensor& A, int64_t shift, int64_t sweeps, int64_t sb) {
@@ -2051,9 +2007,6 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("moead_select_rows(Tensor pop, Tensor off, Tensor win) -> Tensor");
   m.def("moead_select_rows_(Tensor(a!) pop, Tensor off, Tensor win) -> ()");
   m.def("sbr_stats(Tensor A) -> Tensor");
-  m.def("sbr_block(Tensor A, int off, int sweeps, Tensor? dbg=None) -> Tensor[]");
-  m.def("sbr_far(Tensor A, int off, Tensor perm, Tensor Q, Tensor dq, Tensor stats, float thr_fac) -> Tensor");
-  m.def("sbr_bq(Tensor B, int off, Tensor perm, Tensor Q) -> Tensor");
   m.def("sbr_symstats(Tensor T) -> Tensor[]");
   m.def("sbr16_block(Tensor A, int shift, int sweeps, int sb=16) -> Tensor[]");
   m.def("sbr16_far(Tensor A, Tensor perm, Tensor Q, Tensor dq, Tensor stats, float thr_fac, float theta) -> Tensor");
@@ -2150,9 +2103,6 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("moead_select_rows_", &moead_select_rows_);
   m.impl("moead_select_rows", &moead_select_rows);
   m.impl("sbr_stats", &sbr_stats);
-  m.impl("sbr_block", &sbr_block);
-  m.impl("sbr_far", &sbr_far);
-  m.impl("sbr_bq", &sbr_bq);
   m.impl("es_noise_grad", &es_noise_grad);
   m.impl("es_population", &es_population);
   m.impl("knn", &knn);

@@ -314,15 +314,8 @@ void evx_bce_remove(const float* objT, int n, int M, const uint8_t* mask, const 
 void evx_bce_count(const float* pcT, int N, const float* npcT, int Nn, int M, const float* ws, const int64_t* n_nd, uint8_t* out,
                    hipStream_t s);
 // sorted-block refinement of a warm-started eigendecomposition (eigh_sbr.hip, evoxmi/ops/sbr.py)
-int evx_sbr_nblocks(int n, int off);
 int evx_sbr_stat_parts();
 void evx_sbr_stats(const float* A, int n, int64_t lda, double* part, double* out, hipStream_t s);
-void evx_sbr_block(const float* A, int n, int64_t lda, int off, int sweeps, int* perm, float* Q, float* dq, hipStream_t s,
-                   long long* dbg = nullptr);
-void evx_sbr_far(const float* A, int n, int64_t lda, int off, const int* perm, const float* Q, const float* dq,
-                 const double* stats, float thr_fac, float* X, int64_t ldx, hipStream_t s);
-void evx_sbr_bq(const float* B, int rows, int n, int64_t ldb, int off, const int* perm, const float* Q, float* Bq, int64_t ldq,
-                hipStream_t s);
 int evx_sbr_symstats_parts(int n);
 // 16-wide blocks in a shifted sorted order (eigh_sbr16.hip)
 int evx_sbr16_nblocks(int n, int sb);

@@ -1,6 +1,6 @@
 // Sorted-block refinement with 16-wide blocks in a cyclically shifted sorted order (K4, v3).
 //
-// The block step of SBR (eigh_sbr.hip) diagonalises the near (clustered) pairs of the
+// The block step of SBR (evoxmi/ops/sbr.py) diagonalises the near (clustered) pairs of the
 // sorted diagonal exactly.  With 64-wide blocks that is 126 dependent Jacobi rounds per
 // iteration in 16 workgroups (≈134 µs, a third of the converged solve): the chip idles
 // on a latency chain.  Measured on CMA-ES matrices at d = 1000 (CPU reference, five

@@ -71,8 +71,9 @@ def _run(cmd):
     return r.stdout
 
 
-# per-file device flags: the SBR block kernel's register-resident Q rows are updated with
-# scalar FMAs; SLP vectorisation packs them into v_pk ops that need ~3 v_mov shuffles each
+# per-file device flags
+# eigh_sbr.hip: kept so the Taylor operand pass (sbr_taylor_prep_kernel, on the hot path) compiles as it
+# did; whether SLP packing helps or hurts that kernel has not been measured
 # mo_geom.hip: its distance loop must stay unfused (bit-identical ties with the CPU
 # oracle); plain "fast" contraction ignores the in-source pragma
 # neuro.hip: the Ant sub-step is scalar f32 arithmetic; SLP packing adds ~400 v_mov per

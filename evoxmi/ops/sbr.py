@@ -8,13 +8,15 @@ eigenvalue gaps (≈1e-4), so eigenvectors mix over windows of ~60 neighbours ev
 generation and cyclic Jacobi converges only linearly (≈0.5× per 1.1 ms sweep; 2 sweeps
 left a 5e-4 residual in round 1, profiles/r1_jacobi_convergence_probe.log).
 
-Sorted-block refinement (SBR, ``csrc/kernels/eigh_sbr.hip``).  One iteration
-  1. sorts diag(A), cuts the sorted order into 64-blocks (offset 0 / 32 alternately) and
+Sorted-block refinement (SBR, ``csrc/kernels/eigh_sbr16.hip``).  One iteration
+  1. sorts diag(A), shifts the sorted order cyclically (shift 0 / sb/2 on alternate
+     iterations, so rank-adjacent pairs share a block in one of two iterations), cuts it
+     into the blocks [sb·k, sb·k + sb) (sb = 16 or 32, ``SBRConfig.block``) and
      diagonalises each block with two cyclic Jacobi sweeps (near, clustered pairs;
-     ``sbr_block2_kernel``: double-buffered S, one barrier per round, Q in registers);
+     ``sbr16_block_kernel``);
   2. builds the rotation generator X_ij = ½·atan(2·A1_ij / (d_j − d_i)) (the exact 2×2
      Jacobi angle, = A1_ij / (d_j − d_i) to first order) for pairs in different blocks
-     whose gap exceeds ``thr_fac·32·spread/n`` (far pairs);
+     whose gap exceeds ``thr_fac·(sb/2)·spread/n`` (far pairs; ``sbr16_far_kernel``);
   3. caps the step at ‖αX‖₂ ≤ 1 while κ is large (``damping``: 3 block power steps on
      −X²), V = exp(αX) (Paterson–Stockmeyer Taylor, 3 GEMMs), B ← B[:, perm]·Qblk·V,
      Newton–Schulz re-orthonormalisation after large steps, A ← Bᵀ C B (plain GEMMs).
@@ -36,28 +38,16 @@ from __future__ import annotations
 import functools
 import math
 from dataclasses import dataclass, field
-from typing import List
 
 import torch
 
 from . import _ext
 from .linalg import mm
 
-BK = 64
-
-
-def block_starts(n: int, off: int) -> List[int]:
-    starts = ([0] + list(range(off, n, BK))) if off else list(range(0, n, BK))
-    return starts + [n]
-
-
-def nblocks(n: int, off: int) -> int:
-    return len(block_starts(n, off)) - 1
-
 
 # ---------------------------------------------------------------------------- reference
 @functools.lru_cache(maxsize=None)
-def _rr_rounds(m: int = BK):
+def _rr_rounds(m: int):
     """Circle-method round robin on m slots: round r pairs (m−1, r) and
     ((r+i) mod (m−1), (r−i) mod (m−1)), i = 1..m/2−1 — the kernel's pairing."""
     out = []
@@ -108,51 +98,6 @@ def stats_ref(A: torch.Tensor) -> torch.Tensor:
     return torch.stack([off, (d**2).sum(), d.min(), d.max()])
 
 
-def block_solve_ref(A: torch.Tensor, off: int, sweeps: int):
-    n = A.shape[0]
-    d = torch.diagonal(A)
-    perm = torch.argsort(d, stable=True).to(torch.int32)
-    st = block_starts(n, off)
-    nb = len(st) - 1
-    S = torch.zeros(nb, BK, BK, dtype=A.dtype, device=A.device)
-    for k in range(nb):
-        idx = perm[st[k] : st[k + 1]].long()
-        m = idx.numel()
-        S[k, :m, :m] = A[idx][:, idx]
-    S, Q = _block_jacobi_ref(S, sweeps)
-    dq = torch.cat([torch.diagonal(S[k])[: st[k + 1] - st[k]] for k in range(nb)])
-    return perm, Q.contiguous(), dq
-
-
-def _blockdiag(Q: torch.Tensor, n: int, off: int) -> torch.Tensor:
-    st = block_starts(n, off)
-    Qf = torch.zeros(n, n, dtype=Q.dtype, device=Q.device)
-    for k in range(len(st) - 1):
-        m = st[k + 1] - st[k]
-        Qf[st[k] : st[k + 1], st[k] : st[k + 1]] = Q[k, :m, :m]
-    return Qf
-
-
-def far_ref(A, off, perm, Q, dq, stats, thr_fac):
-    n = A.shape[0]
-    p = perm.long()
-    Qf = _blockdiag(Q, n, off)
-    A1 = Qf.T @ A[p][:, p] @ Qf
-    st = block_starts(n, off)
-    blk = torch.zeros(n, dtype=torch.long, device=A.device)
-    for k in range(len(st) - 1):
-        blk[st[k] : st[k + 1]] = k
-    den = dq[None, :] - dq[:, None]
-    thr = thr_fac * (0.5 * BK) * float(stats[3] - stats[2]) / n
-    mask = (blk[None, :] != blk[:, None]) & (den.abs() > thr)
-    # the 2×2 Jacobi angle ½·atan(2a/den): first-order a/den for separated pairs, ≤ π/4
-    return torch.where(mask, 0.5 * torch.atan(2 * A1 / torch.where(mask, den, torch.ones_like(den))), torch.zeros_like(A1))
-
-
-def bq_ref(B, off, perm, Q):
-    return B[:, perm.long()] @ _blockdiag(Q, B.shape[1], off)
-
-
 # ------------------------------------------------- 16-wide blocks, shifted sorted order
 # (csrc/kernels/eigh_sbr16.hip): position j of the order is index argsort(diag)[(j + shift)
 # mod n] and blocks are always [16k, 16k + 16) — shift 0 / 8 on alternate iterations.
@@ -167,6 +112,7 @@ def perm_shift_ref(A: torch.Tensor, shift: int) -> torch.Tensor:
 
 
 SHIFT_BLOCKS = (16, 32)  # block sizes of the shifted layout (eigh_sbr16.hip templates)
+DEFAULT_BLOCK = 32       # SBRConfig.block and the bk of block_solve / far / bq
 
 
 def block_solve16_ref(A: torch.Tensor, shift: int, sweeps: int, sb: int = SB):
@@ -241,32 +187,22 @@ def stats(A):
     return _ext.ops().sbr_stats(_rowmajor(A)) if _dev(A) else stats_ref(A)
 
 
-def block_solve(A, off, sweeps, bk: int = BK):
-    if bk in SHIFT_BLOCKS:
-        if _dev(A):
-            return tuple(_ext.ops().sbr16_block(_rowmajor(A), int(off) % A.shape[0], int(sweeps), int(bk)))
-        return block_solve16_ref(A, off, sweeps, bk)
+def block_solve(A, off, sweeps, bk: int = DEFAULT_BLOCK):
     if _dev(A):
-        perm, Q, dq = _ext.ops().sbr_block(_rowmajor(A), int(off), int(sweeps))
-        return perm, Q, dq
-    return block_solve_ref(A, off, sweeps)
+        return tuple(_ext.ops().sbr16_block(_rowmajor(A), int(off) % A.shape[0], int(sweeps), int(bk)))
+    return block_solve16_ref(A, off, sweeps, bk)
 
 
-def far(A, off, perm, Q, dq, st, thr_fac, bk: int = BK, theta: float = None):
+# far / bq read the layout from perm (already shifted) and the block size from Q's shape
+def far(A, off, perm, Q, dq, st, thr_fac, bk: int = DEFAULT_BLOCK, theta: float = None):
     theta = LOCAL_THETA if theta is None else theta
-    if bk in SHIFT_BLOCKS:
-        if _dev(A):
-            return _ext.ops().sbr16_far(_rowmajor(A), perm, Q, dq, st, float(thr_fac), float(theta))
-        return far16_ref(A, perm, Q, dq, st, thr_fac, theta)
     if _dev(A):
-        return _ext.ops().sbr_far(_rowmajor(A), int(off), perm, Q, dq, st, float(thr_fac))
-    return far_ref(A, off, perm, Q, dq, st, thr_fac)
+        return _ext.ops().sbr16_far(_rowmajor(A), perm, Q, dq, st, float(thr_fac), float(theta))
+    return far16_ref(A, perm, Q, dq, st, thr_fac, theta)
 
 
-def bq(B, off, perm, Q, bk: int = BK):
-    if bk in SHIFT_BLOCKS:
-        return _ext.ops().sbr16_bq(_rowmajor(B), perm, Q) if _dev(B) else bq16_ref(B, perm, Q)
-    return _ext.ops().sbr_bq(_rowmajor(B), int(off), perm, Q) if _dev(B) else bq_ref(B, off, perm, Q)
+def bq(B, off, perm, Q, bk: int = DEFAULT_BLOCK):
+    return _ext.ops().sbr16_bq(_rowmajor(B), perm, Q) if _dev(B) else bq16_ref(B, perm, Q)
 
 
 def expm_taylor6(X: torch.Tensor, X2: torch.Tensor = None, alpha: torch.Tensor = None) -> torch.Tensor:
@@ -410,8 +346,8 @@ class SBRConfig:
     theta_kappa: float = 0.05
     max_jacobi: int = 16
     block_sweeps: int = 2
-    block: int = 32            # 16 / 32: blocks in a shifted sorted order (eigh_sbr16.hip; 16 = one
-                               # wave per block, 32 = four); 64: the 64-wide offset layout (eigh_sbr.hip)
+    block: int = DEFAULT_BLOCK  # 16 / 32: blocks in a shifted sorted order (eigh_sbr16.hip; 16 = one
+                               # wave per block, 32 = four)
     thr_fac: float = None      # far-pair threshold factor (default 0.3)
     ns_iters: int = 2          # Newton–Schulz re-orthonormalisation in the first iterations and
                                # after every damped one (undamped later ones have ‖X‖₂ ≲ 0.5:
@@ -422,8 +358,8 @@ class SBRConfig:
     def __post_init__(self):
         if self.thr_fac is None:
             self.thr_fac = 0.3
-        if self.block not in SHIFT_BLOCKS + (BK,):
-            raise ValueError(f"SBR block size must be one of {SHIFT_BLOCKS + (BK,)}, got {self.block}")
+        if self.block not in SHIFT_BLOCKS:
+            raise ValueError(f"SBR block size must be one of {SHIFT_BLOCKS}, got {self.block}")
 
 
 def _read(st: torch.Tensor):
@@ -749,7 +685,7 @@ def eigh_warm(C: torch.Tensor, B_prev: torch.Tensor, cfg: SBRConfig = None, plan
         # an undamped far iteration close to the tolerance that barely helps: pairs inside a
         # cluster denser than the global threshold assumes are neither far nor in a block —
         # the local threshold takes them into the far step for the rest of the solve
-        if far_on and alpha >= 1.0 and off_rel < 100 * cfg.tol and off_rel > 0.6 * prev and cfg.block in SHIFT_BLOCKS:
+        if far_on and alpha >= 1.0 and off_rel < 100 * cfg.tol and off_rel > 0.6 * prev:
             theta = 1.0
         last_far = far_on
         prev = off_rel

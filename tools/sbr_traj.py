@@ -21,7 +21,7 @@ from evoxmi.workflows import StdWorkflow  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--gens", type=int, default=35)
 ap.add_argument("--save", type=int, nargs="*", default=[])
-ap.add_argument("--variants", default="16:0.3:1:3,16:0.5:1:3,16:0.3:1:0,64:0.3:0:3", help="block:thr_fac:local_theta:near_only,...")
+ap.add_argument("--variants", default="16:0.3:1:3,16:0.5:1:3,16:0.3:1:0", help="block:thr_fac:local_theta:near_only,...")
 a = ap.parse_args()
 dev = torch.device("cuda")
 rec = []
@@ -30,7 +30,7 @@ orig = sbr.eigh_warm
 
 def hook(C, B_prev, cfg=None, plans=None):
     rec.append((C.detach().clone(), B_prev.detach().clone()))
-    return orig(C, B_prev, sbr.SBRConfig(tol=cfg.tol if cfg else 1e-5, block=64))
+    return orig(C, B_prev, sbr.SBRConfig(tol=cfg.tol if cfg else 1e-5))
 
 
 sbr.eigh_warm = hook
