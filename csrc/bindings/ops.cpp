@@ -1624,6 +1624,40 @@ std::vector<at::Tensor> bige_estimate(const at::Tensor& fit, const at::Tensor& m
   return {bi, pr, cd};
 }
 
+// hv_exact.hip: the total (a 0-d float64) or the contributions (n,) float64 of the boxes [0, p_i].  pT is the (m, n) transpose of the
+// points clamped at 0, vals and idx its rows sorted descending by a stable sort (evoxmi/ops/hv.py does that)
+static at::Tensor hv_run(const char* name, const at::Tensor& pT, const at::Tensor& vals, const at::Tensor& idx, bool contributions) {
+  CHECK_DEV(pT); CHECK_F32(pT); CHECK_CONTIG(pT); CHECK_DEV(vals); CHECK_F32(vals); CHECK_CONTIG(vals); CHECK_DEV(idx); CHECK_CONTIG(idx);
+  TORCH_CHECK(pT.dim() == 2, name, ": pT float32 (m, n)");
+  const int64_t m = pT.size(0), n = pT.size(1);
+  TORCH_CHECK(vals.sizes() == pT.sizes() && idx.sizes() == pT.sizes() && idx.scalar_type() == at::kLong, name,
+              ": vals float32 and idx int64, both (m, n)");
+  TORCH_CHECK(vals.device() == pT.device() && idx.device() == pT.device(), name, ": one device");
+  TORCH_CHECK(m >= 2 && m <= (contributions ? 3 : 4), name, ": 2 <= m <= ", contributions ? 3 : 4);
+  const int64_t cap = m == (contributions ? 3 : 4) ? evx_hv_owned_max_n() : 32768;
+  TORCH_CHECK(n >= 1 && n <= cap, name, ": 1 <= n <= ", cap, " at m = ", m);
+  c10::DeviceGuard g(pT.device());
+  auto i32 = at::empty({6, n}, pT.options().dtype(at::kInt));  // zrank, wrank, orig, X, Y, ZW
+  auto f64 = at::empty({3, n}, pT.options().dtype(at::kDouble));  // h, g, scratch
+  auto out = at::empty({contributions ? n : 1}, pT.options().dtype(at::kDouble));
+  int* w = i32.data_ptr<int>();
+  double* d = f64.data_ptr<double>();
+  uint32_t* u = reinterpret_cast<uint32_t*>(w + 3 * n);
+  if (contributions)
+    evx_hv_contributions(pT.data_ptr<float>(), vals.data_ptr<float>(), idx.data_ptr<int64_t>(), (int)n, (int)m, w, w + n, d, d + n, u, u + n,
+                         u + 2 * n, w + 2 * n, out.data_ptr<double>(), cur_stream());
+  else
+    evx_hv_exact(pT.data_ptr<float>(), vals.data_ptr<float>(), idx.data_ptr<int64_t>(), (int)n, (int)m, w, w + n, d, d + n, u, u + n, u + 2 * n,
+                 w + 2 * n, d + 2 * n, out.data_ptr<double>(), cur_stream());
+  return contributions ? out : out.reshape({});
+}
+
+at::Tensor hv_exact(const at::Tensor& pT, const at::Tensor& vals, const at::Tensor& idx) { return hv_run("hv_exact", pT, vals, idx, false); }
+
+at::Tensor hv_contributions(const at::Tensor& pT, const at::Tensor& vals, const at::Tensor& idx) {
+  return hv_run("hv_contributions", pT, vals, idx, true);
+}
+
 // t_rank (n,) float32, then cls (n,) int32 and val (n,) float64 of tdea_select.hip on rvea_select.hip's best cosine: the θ-rank of
 // the masked rows of obj (n, m) on the directions w (nw, m); theta is (nw,) float32
 std::vector<at::Tensor> tdea_theta_rank(const at::Tensor& obj, const at::Tensor& w, const at::Tensor& theta, const at::Tensor& mask) {
@@ -1984,6 +2018,8 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("rvea_cos_best(Tensor A, Tensor? shift, float? floor, Tensor B, bool clamp, bool self_zero) -> Tensor[]");
   m.def("rvea_select(Tensor f, Tensor? shift, float? floor, Tensor v, Tensor theta) -> Tensor[]");
   m.def("bige_estimate(Tensor fit, Tensor mask, Tensor r) -> Tensor[]");
+  m.def("hv_exact(Tensor pT, Tensor vals, Tensor idx) -> Tensor");
+  m.def("hv_contributions(Tensor pT, Tensor vals, Tensor idx) -> Tensor");
   m.def("tdea_theta_rank(Tensor obj, Tensor w, Tensor theta, Tensor mask) -> Tensor[]");
   m.def("sra_rank(Tensor I1, Tensor I2, Tensor u, Tensor pc) -> Tensor");
   m.def("sra_indicators(Tensor obj) -> Tensor[]");
@@ -2087,6 +2123,8 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("rvea_cos_best", &rvea_cos_best);
   m.impl("rvea_select", &rvea_select);
   m.impl("bige_estimate", &bige_estimate);
+  m.impl("hv_exact", &hv_exact);
+  m.impl("hv_contributions", &hv_contributions);
   m.impl("tdea_theta_rank", &tdea_theta_rank);
   m.impl("sra_rank", &sra_rank);
   m.impl("sra_indicators", &sra_indicators);

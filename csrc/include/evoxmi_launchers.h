@@ -266,6 +266,16 @@ void evx_rvea_pick(const int* arg, const double* apd, int n, int nv, const uint6
 // word
 void evx_bige_estimate(const float* f, const bool* mask, const float* r, int n, int m, float* fmin, float* fmax, double* x, double* prs,
                        float* bi, double* pr, double* cd, hipStream_t s);
+// hv_exact.hip: the exact hypervolume of the boxes [0, p_i] (m = 2, 3, 4) and every row's exclusive contribution (m = 2, 3); the
+// contract is in evoxmi/ops/hv.py.  pT is the (m, n) transpose of the points clamped at 0, vals and idx (m, n) its rows sorted
+// descending by a stable sort and their original positions.  Scratch of n words each: zrank, wrank, orig, X, Y, ZW, h, g (and
+// scratch for the total).  out is one word (total) or (n,) (contributions).  n ≤ 32768, and n ≤ evx_hv_owned_max_n() for the total
+// at m = 4 and the contributions at m = 3
+int evx_hv_owned_max_n();
+void evx_hv_exact(const float* pT, const float* vals, const int64_t* idx, int n, int m, int* zrank, int* wrank, double* h, double* g,
+                  uint32_t* X, uint32_t* Y, uint32_t* ZW, int* orig, double* scratch, double* out, hipStream_t s);
+void evx_hv_contributions(const float* pT, const float* vals, const int64_t* idx, int n, int m, int* zrank, int* wrank, double* h, double* g,
+                          uint32_t* X, uint32_t* Y, uint32_t* ZW, int* orig, double* out, hipStream_t s);
 // tdea_select.hip: θ-DEA's θ-ranking (the contract is in evoxmi/ops/tdea.py) from best and arg (n each) of
 // evx_rvea_cos_best, mode 0, of obj (n, m) against the nw directions: cls and val (n each), then t_rank (n,) float32, the
 // rank of every masked row among the masked rows of its cls, +inf outside the mask; theta is (nw,) float32

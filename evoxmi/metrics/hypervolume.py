@@ -5,7 +5,9 @@
 * ``each_cube_monte_carlo_hv`` — per-point boxes, each sample weighted by
   1/(number of points dominating it) (the reference's bincount form);
 * ``exact_hv`` — exact value by slicing (HSO) for any m, O(n^{m−1} log n), meant for
-  fronts of moderate size / validation of the estimators.
+  fronts of moderate size / validation of the estimators;
+* ``hv_exact``, ``hv_contributions``, ``ExactHV`` — the exact value and every point's exclusive contribution on the
+  device for m ≤ 4 (``ops.hv``: a masked staircase scan, no host read, capturable).
 
 Both estimators reduce to per-sample dominator counts (samples × points × m comparisons):
 one tiled HIP kernel on the GPU (``ops.geom.hv_count``), chunked torch on the CPU.  Like the reference, points are measured as |objs − ref|
@@ -17,6 +19,7 @@ import numpy as np
 import torch
 
 from ..ops import geom
+from ..ops import hv as hv_ops
 from ..ops import random as rnd
 
 def _dominated_counts(samples, points):
@@ -74,6 +77,36 @@ def _hso(pts: np.ndarray) -> float:
 def exact_hv(objs, ref) -> float:
     pts = torch.abs(torch.as_tensor(objs, dtype=torch.float64) - torch.as_tensor(ref, dtype=torch.float64)).cpu().numpy()
     return _hso(pts)
+
+
+def _points(objs, ref):
+    objs = torch.as_tensor(objs)
+    return torch.abs(objs - torch.as_tensor(ref, dtype=objs.dtype, device=objs.device))
+
+
+def hv_exact(objs, ref):
+    """The exact hypervolume of ``objs (n, m)``, m = 2, 3, 4, measured as |objs − ref|: a 0-d float64 tensor on the
+    device of ``objs`` (``ops.hv.exact``: kernels for float32 on a HIP device, nothing read on the host)."""
+    return hv_ops.exact(_points(objs, ref))
+
+
+def hv_contributions(objs, ref):
+    """Every point's exclusive contribution ``HV(objs) − HV(objs without i)``, m = 2, 3: ``(n,)`` float64 on the device
+    of ``objs`` (``ops.hv.contributions``)."""
+    return hv_ops.contributions(_points(objs, ref))
+
+
+class ExactHV:
+    """The exact hypervolume with respect to ``ref`` as a device scalar; ``.contributions`` ranks or prunes a front."""
+
+    def __init__(self, ref):
+        self.ref = ref
+
+    def __call__(self, objs):
+        return hv_exact(objs, self.ref)
+
+    def contributions(self, objs):
+        return hv_contributions(objs, self.ref)
 
 
 class HV:

@@ -85,12 +85,13 @@ def _run(cmd):
 # rvea_select.hip: the same kind of contract: its cosines are symmetric bit for bit and a host implementation reproduces them
 # bige_select.hip, tdea_select.hip: the same kind of contract: a host implementation reproduces BiGE's proximity and θ-DEA's
 # penalised distance bit for bit
+# hv_exact.hip: its accuracy contract counts one rounding per float64 operation of the stated formulas, so none may fuse
 # planar_rollout.hip: as neuro.hip, its sub-step is scalar f32 arithmetic; SLP packing adds ~190 v_mov per
 # sub-step (835 instructions against 704 without it in the two-chain instantiation)
 FILE_FLAGS = {"eigh_sbr.hip": ["-fno-slp-vectorize"], "mo_geom.hip": ["-ffp-contract=fast-honor-pragmas"],
               "knea_select.hip": ["-ffp-contract=off"], "rvea_select.hip": ["-ffp-contract=off"],
               "bige_select.hip": ["-ffp-contract=off"], "tdea_select.hip": ["-ffp-contract=off"],
-              "rng.hip": ["-ffp-contract=fast-honor-pragmas"],
+              "hv_exact.hip": ["-ffp-contract=off"], "rng.hip": ["-ffp-contract=fast-honor-pragmas"],
               "neuro.hip": ["-fno-slp-vectorize"], "planar_rollout.hip": ["-fno-slp-vectorize"], "gemm_ks.hip": ["-fno-slp-vectorize"]}
 
 
