@@ -1761,6 +1761,15 @@ std::vector<at::Tensor> spea2_fitness(const at::Tensor& obj) {
   return {sig, S, R, D, nd, msk, nn_d2, nn_idx};
 }
 
+// (M, n): the transpose zero padded to the removal kernels' compile-time objective counts, M = evx_padded_m(m).  A thread's rows are
+// n-strided and its loads coalesced; zero rows add nothing to a squared distance
+at::Tensor padded_transpose(const at::Tensor& obj) {
+  const int64_t n = obj.size(0), m = obj.size(1), M = evx_padded_m((int)m);
+  auto objT = at::zeros({M, n}, obj.options());
+  objT.narrow(0, 0, m).copy_(obj.t());
+  return objT;
+}
+
 // keep, order, {rescans, removed}; without (nn_d2, nn_idx) the neighbour pass runs first for the given mask
 std::vector<at::Tensor> spea2_truncate(const at::Tensor& obj, const at::Tensor& mask, int64_t n_keep,
                                        const c10::optional<at::Tensor>& nn_d2, const c10::optional<at::Tensor>& nn_idx) {
@@ -1788,23 +1797,14 @@ std::vector<at::Tensor> spea2_truncate(const at::Tensor& obj, const at::Tensor& 
     evx_spea2_neighbours(obj.data_ptr<float>(), (int)n, (int)m, (const uint8_t*)mask.data_ptr<bool>(), d2v.data_ptr<float>(),
                          idxv.data_ptr<int32_t>(), cur_stream());
   }
-  const int64_t M = evx_spea2_padded_m((int)m), n_order = std::max<int64_t>(n - n_keep, 0);
-  auto objT = at::zeros({M, n}, obj.options());  // (M, n): a thread's rows are n-strided, its loads coalesced; zero rows add nothing to d2
-  objT.narrow(0, 0, m).copy_(obj.t());
+  const int64_t n_order = std::max<int64_t>(n - n_keep, 0);
+  const at::Tensor objT = padded_transpose(obj);
   auto keep = at::empty({n}, obj.options().dtype(at::kBool)), order = at::empty({n_order}, obj.options().dtype(at::kLong));
   auto stats = at::empty({2}, obj.options().dtype(at::kInt));
-  evx_spea2_truncate(objT.data_ptr<float>(), (int)n, (int)M, (const uint8_t*)mask.data_ptr<bool>(), d2v.data_ptr<float>(),
+  evx_spea2_truncate(objT.data_ptr<float>(), (int)n, (int)objT.size(0), (const uint8_t*)mask.data_ptr<bool>(), d2v.data_ptr<float>(),
                      idxv.data_ptr<int32_t>(), (int)n_keep, (uint8_t*)keep.data_ptr<bool>(), order.data_ptr<int64_t>(), (int)n_order,
                      stats.data_ptr<int32_t>(), cur_stream());
   return {keep, order, stats};
-}
-
-// (M, n): the transpose zero padded to the kernels' compile-time objective counts
-at::Tensor bce_transposed(const at::Tensor& obj) {
-  const int64_t n = obj.size(0), m = obj.size(1), M = evx_bce_padded_m((int)m);
-  auto objT = at::zeros({M, n}, obj.options());
-  objT.narrow(0, 0, m).copy_(obj.t());
-  return objT;
 }
 
 void bce_check(const at::Tensor& obj, const char* who) {
@@ -1826,7 +1826,7 @@ std::vector<at::Tensor> bce_niche(const at::Tensor& obj, const c10::optional<at:
     mp = (const uint8_t*)mask->data_ptr<bool>();
   }
   c10::DeviceGuard g(obj.device());
-  const at::Tensor objT = bce_transposed(obj);
+  const at::Tensor objT = padded_transpose(obj);
   auto t = at::empty({n}, obj.options()), ws = at::empty({evx_bce_ws_floats()}, obj.options());
   auto cnt = at::empty({}, obj.options().dtype(at::kLong));
   evx_bce_niche(objT.data_ptr<float>(), (int)n, (int)objT.size(0), mp, t.data_ptr<float>(), ws.data_ptr<float>(), cnt.data_ptr<int64_t>(),
@@ -1840,7 +1840,7 @@ std::vector<at::Tensor> bce_pc_select(const at::Tensor& obj, int64_t n_keep, con
   const int64_t n = obj.size(0);
   TORCH_CHECK(n_keep >= 1, "bce_pc_select: need n_keep >= 1");
   c10::DeviceGuard g(obj.device());
-  const at::Tensor objT = bce_transposed(obj);
+  const at::Tensor objT = padded_transpose(obj);
   const int M = (int)objT.size(0);
   at::Tensor msk;
   if (mask.has_value()) {
@@ -1875,7 +1875,7 @@ at::Tensor bce_explore(const at::Tensor& pc_obj, const at::Tensor& npc_obj, cons
   TORCH_CHECK(n_nd.scalar_type() == at::kLong && n_nd.numel() == 1 && n_nd.device() == pc_obj.device(), "bce_explore: n_nd one int64 word");
   const int64_t N = pc_obj.size(0);
   c10::DeviceGuard g(pc_obj.device());
-  const at::Tensor pcT = bce_transposed(pc_obj), npcT = bce_transposed(npc_obj);
+  const at::Tensor pcT = padded_transpose(pc_obj), npcT = padded_transpose(npc_obj);
   auto t = at::empty({N}, pc_obj.options()), ws = at::empty({evx_bce_ws_floats()}, pc_obj.options());
   auto cnt = at::empty({}, pc_obj.options().dtype(at::kLong)), out = at::empty({N}, pc_obj.options().dtype(at::kBool));
   evx_bce_niche(pcT.data_ptr<float>(), (int)N, (int)pcT.size(0), nullptr, t.data_ptr<float>(), ws.data_ptr<float>(), cnt.data_ptr<int64_t>(),

@@ -68,6 +68,53 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_prod(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v *= __shfl_xor(v, o, 64);
+  return v;
+}
+// 64-bit keys ((value image, index) words): the unsigned minimum / maximum
+__device__ __forceinline__ unsigned long long wave_min(unsigned long long k) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long q = __shfl_xor(k, o, 64);
+    k = q < k ? q : k;
+  }
+  return k;
+}
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long k) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long q = __shfl_xor(k, o, 64);
+    k = q > k ? q : k;
+  }
+  return k;
+}
+// a wave-uniform word into scalar registers
+__device__ __forceinline__ unsigned long long uniform(unsigned long long k) {
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(k >> 32));
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)k);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// torch's amax / amin: a NaN wins (fmaxf / fminf drop it); wave_nan_max leaves the result in every lane
+__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
+__device__ __forceinline__ float nan_min(float a, float b) { return (b < a || b != b) ? b : a; }
+__device__ __forceinline__ float wave_nan_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = nan_max(v, __shfl_xor(v, o, 64));
+  return v;
+}
 
 // block-wide sum; `scratch` holds >= blockDim/64 floats; result broadcast to all
 __device__ __forceinline__ float block_sum(float v, float* scratch) {

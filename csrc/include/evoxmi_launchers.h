@@ -294,20 +294,21 @@ int evx_ibea_max_m();
 void evx_ibea_fitness(const float* obj, int n, int m, float kappa, float* f, float* C, hipStream_t s);
 void evx_ibea_truncate(const float* objT, const float* f, const float* C, float kappa, int n, int m, int n_remove, int n_keep,
                        int64_t* idx, int64_t* order, hipStream_t s);
+// the objective counts the one-workgroup removal kernels (spea2_select.hip, bce_select.hip) are compiled for: m is zero padded to this
+inline int evx_padded_m(int m) { return m <= 2 ? 2 : m == 3 ? 3 : m == 4 ? 4 : m <= 8 ? 8 : 16; }
 // spea2_select.hip: SPEA2's fitness in two launches (n ≤ evx_spea2_fitness_max_n(), m ≤ evx_spea2_max_m(): S, nd, msk = nd without NaN rows,
 // D, R, sig = D + R and the nearest neighbour (nn_d2, nn_idx) of every row of msk among the others), the neighbour pass alone for a given mask,
-// and the truncation on one workgroup (objT the (M, n) transpose zero padded to M = evx_spea2_padded_m(m) rows, n ≤ evx_spea2_max_n();
+// and the truncation on one workgroup (objT the (M, n) transpose zero padded to M = evx_padded_m(m) rows, n ≤ evx_spea2_max_n();
 // keep (n,) the masked rows that stay, order (n_order,) the removed rows then −1, stats = {rescans, removed})
 int evx_spea2_max_n();
 int evx_spea2_fitness_max_n();
 int evx_spea2_max_m();
-int evx_spea2_padded_m(int m);
 void evx_spea2_fitness(const float* obj, int n, int m, int32_t* S, uint8_t* nd, uint8_t* msk, float* D, float* R, float* sig,
                        float* nn_d2, int32_t* nn_idx, hipStream_t s);
 void evx_spea2_neighbours(const float* obj, int n, int m, const uint8_t* mask, float* nn_d2, int32_t* nn_idx, hipStream_t s);
 void evx_spea2_truncate(const float* objT, int n, int M, const uint8_t* mask, const float* nn_d2, const int32_t* nn_idx, int n_keep,
                         uint8_t* keep, int64_t* order, int n_order, int32_t* stats, hipStream_t s);
-// bce_select.hip: BCE-IBEA's PC selection and exploration (objT the (M, n) transpose zero padded to M = evx_bce_padded_m(m) rows;
+// bce_select.hip: BCE-IBEA's PC selection and exploration (objT the (M, n) transpose zero padded to M = evx_padded_m(m) rows;
 // ws evx_bce_ws_floats() floats: the spans and, last, the niche radius; cnt one word, the rows of the mask).  evx_bce_mask: the rows no
 // row dominates; evx_bce_niche: spans, t (n,) and the radius over the masked rows (mask == nullptr: all; with n_keep ≥ 0 t and the radius
 // are left unwritten where cnt ≤ n_keep, as are the scores: nothing will be removed); evx_bce_remove: the scores and
@@ -315,7 +316,6 @@ void evx_spea2_truncate(const float* objT, int n, int M, const uint8_t* mask, co
 // most one NPC row within n_nd / N · radius of PC row i
 int evx_bce_max_n();
 int evx_bce_max_m();
-int evx_bce_padded_m(int m);
 int evx_bce_ws_floats();
 void evx_bce_mask(const float* objT, int n, int M, uint8_t* mask, hipStream_t s);
 void evx_bce_niche(const float* objT, int n, int M, const uint8_t* mask, float* t, float* ws, int64_t* cnt, int n_keep, hipStream_t s);

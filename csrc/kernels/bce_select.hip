@@ -3,7 +3,7 @@
 // m ≤ 16 objectives, which arrive transposed and zero padded to M ∈ {2, 3, 4, 8, 16} rows, (M, n).
 //
 // The contract (the float64 reference of the tests implements the same formulas):
-//   mask     the rows that no row dominates (all ≤ and any <; NaN compares false), or the caller's mask;
+//   mask     the rows that no row dominates (the test of evx::dominates), or the caller's mask;
 //            n_nd its count
 //   span_k   max(f_max_k − f_min_k, 1e-12) over the masked rows (fminf / fmaxf; a padded objective gets 1e-12
 //            and contributes δ = 0)
@@ -108,9 +108,7 @@
 //   bce_remove<16, 8, 512>         170   0     106   0        17184
 //   bce_remove<16, 16, 512>        194   0     106   0        16928
 // 256 threads are one wave per SIMD, 512 threads two (256 VGPRs each).
-#include <type_traits>
-
-#include "evoxmi_common.h"
+#include "evoxmi_mo.h"
 
 namespace {
 
@@ -146,30 +144,7 @@ __device__ __forceinline__ float factor(float d, float r) {
 __device__ __forceinline__ unsigned long long arg_key(float P, int C, int row) {
   // C counts the absorbing factors apart: NaN factors in its low half, zero factors in its high half
   const uint32_t s = (C & 0xffff) ? 0xffffffffu : 0x7fffffffu - ((C >> 16) ? 0u : __float_as_uint(P));  // +0 ≤ P ≤ 1: its bits are ordered
-  return ((unsigned long long)s << 32) | (uint32_t)~row;
-}
-__device__ __forceinline__ unsigned long long wave_max_key(unsigned long long k) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long q = __shfl_xor(k, o, 64);
-    k = q > k ? q : k;
-  }
-  return k;
-}
-__device__ __forceinline__ unsigned long long uniform_key(unsigned long long k) {
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(k >> 32));
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)k);
-  return ((unsigned long long)hi << 32) | lo;
-}
-__device__ __forceinline__ float wave_prod(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v *= __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_isum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
+  return evx::key64(s, (uint32_t)~row);
 }
 
 // mask[i] = no row dominates row i
@@ -183,7 +158,7 @@ __global__ void __launch_bounds__(BC_GRID_THREADS) bce_mask_kernel(const float* 
   const float* oi = js[wave];
   bool dominated = false;
   for (int j = lane; j < n; j += 64) {
-    bool le = true, lt = false;  // row j dominates row i
+    bool le = true, lt = false;  // row j dominates row i; not evx::dominates: with it the kernel takes two more SGPRs
     for (int k = 0; k < M; ++k) {
       const float x = oT[(int64_t)k * n + j], y = oi[k];
       le &= x <= y;
@@ -217,7 +192,7 @@ __global__ void __launch_bounds__(256) bce_bounds_kernel(const float* __restrict
     }
     lo = evx::wave_min(lo);
     hi = evx::wave_max(hi);
-    c = wave_isum(c);
+    c = evx::wave_sum(c);
     __syncthreads();  // the previous objective's partials are consumed
     if (lane == 0) {
       lo_s[wave] = lo;
@@ -322,9 +297,9 @@ __global__ void __launch_bounds__(BC_GRID_THREADS) bce_score_kernel(const float*
         }
       }
     }
-    prod *= wave_prod(pw);
+    prod *= evx::wave_prod(pw);
   }
-  nans = wave_isum(nans);
+  nans = evx::wave_sum(nans);
   if (lane == 0) {
     P[j] = prod;
     C[j] = nans;
@@ -351,14 +326,10 @@ __global__ void __launch_bounds__(BC_GRID_THREADS) bce_count_kernel(const float*
     const float d = nd2([&](int k) { return oi[k]; }, [&](int k) { return npcT[(int64_t)k * Nn + j]; }, [&](int k) { return sp[k]; }, M);
     c += d <= thr ? 1 : 0;
   }
-  c = wave_isum(c);
+  c = evx::wave_sum(c);
   if (lane == 0) out[i] = c <= 1 ? 1 : 0;
 }
 
-struct alignas(16) BcPart {
-  unsigned long long key;
-  int cnt;
-};
 struct alignas(8) BcProd {
   float p;
   int c;
@@ -378,12 +349,12 @@ __global__ void __launch_bounds__(TB) bce_remove_kernel(const float* __restrict_
   // rows per unrolled group: all of them while they live in registers (one group: own[u] is own[i]); re-read rows in groups that keep
   // 64 loads in flight, not IT·M registers
   constexpr int UNR = REG ? IT : M <= 4 ? (IT < 8 ? IT : 8) : (IT < 4 ? IT : 4);
-  __shared__ BcPart partF[2][BC_WAVES];
+  __shared__ evx::RemovalPart partF[2][BC_WAVES];
   __shared__ BcProd partP[2][8][B];
   __shared__ uint16_t wlist[BC_MAX_N];  // wave w: entries w·64·IT …
   __shared__ int wcount[BC_WAVES];
-  constexpr int lg = TB == 256 ? 8 : 9, nt = TB, nw = TB >> 6;
-  static_assert(TB == 256 || TB == 512, "a power of two, at most BC_THREADS");
+  using Shape = evx::RemovalShape<TB>;
+  constexpr int lg = Shape::lg, nt = Shape::nt, nw = Shape::nw;
   const int r = threadIdx.x, lane = r & 63, wave = r >> 6;
   const unsigned long long below = (1ull << lane) - 1ull;
 
@@ -421,7 +392,9 @@ __global__ void __launch_bounds__(TB) bce_remove_kernel(const float* __restrict_
 #pragma unroll
     for (int k = 0; k < MO; ++k) own[i][k] = (REG && p < n) ? oT[(int64_t)k * n + p] : 0.f;
   }
-  int c = wave_isum(__popc(live));
+  // the count and the target lookup below are the same in spea2_select.hip and bce_select.hip and stay written out: as shared
+  // helpers their unrolled wave loops are reassociated before inlining and every instantiation's code length changes
+  const int c = evx::wave_sum((int)__popc(live));
   if (lane == 0) wcount[wave] = c;
   __syncthreads();
   int count = 0;
@@ -474,22 +447,20 @@ __global__ void __launch_bounds__(TB) bce_remove_kernel(const float* __restrict_
       const int p = r + (i << lg);
       const bool on = (live >> i) & 1u;
       const bool flag = (fl >> i) & 1u;
-      const unsigned long long bal = __ballot(flag);
-      if (flag) wlist[wave * (64 * IT) + cw + __popcll(bal & below)] = (uint16_t)p;
-      cw += __popcll(bal);
+      cw = evx::wave_append(flag, (uint16_t)p, wlist + wave * (64 * IT), cw, below);
       if (on && !flag) {
         const unsigned long long q = arg_key(P[i], C[i], p);
         key = q > key ? q : key;
       }
     }
-    key = wave_max_key(key);
-    if (lane == 0) partF[buf][wave] = BcPart{key, cw};
+    key = evx::wave_max(key);
+    if (lane == 0) partF[buf][wave] = evx::RemovalPart{key, cw};
     __syncthreads();
     int total = 0;
     key = BC_NO_KEY;
     for (int w = 0; w < nw; ++w) {
-      const BcPart q = partF[buf][w];
-      const unsigned long long qk = uniform_key(q.key);
+      const evx::RemovalPart q = partF[buf][w];
+      const unsigned long long qk = evx::uniform(q.key);
       total += __builtin_amdgcn_readfirstlane(q.cnt);
       key = qk > key ? qk : key;
     }
@@ -541,10 +512,10 @@ __global__ void __launch_bounds__(TB) bce_remove_kernel(const float* __restrict_
       }
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
-        const int cs = wave_isum(cn[b]);
+        const int cs = evx::wave_sum(cn[b]);
 #pragma unroll
         for (int q = 0; q < NC; ++q) {
-          const float v = wave_prod(pr[b][q]);
+          const float v = evx::wave_prod(pr[b][q]);
           if (lane == 0) partP[pq][wave + q * nw][b] = BcProd{v, q == 0 ? cs : 0};
         }
       }
@@ -566,7 +537,7 @@ __global__ void __launch_bounds__(TB) bce_remove_kernel(const float* __restrict_
           P[i] = hit ? np : P[i];
           C[i] = hit ? nc : C[i];
         }
-        const unsigned long long ak = uniform_key(arg_key(np, nc, tg[b]));
+        const unsigned long long ak = evx::uniform(arg_key(np, nc, tg[b]));
         key = ak > key ? ak : key;
       }
       pq ^= 1;
@@ -599,33 +570,7 @@ __global__ void __launch_bounds__(TB) bce_remove_kernel(const float* __restrict_
     x = key == BC_NO_KEY ? -1 : (int)~(uint32_t)key;
   }
 
-#pragma unroll
-  for (int i = 0; i < IT; ++i) {
-    const int p = r + (i << lg);
-    if (p < n) keep[p] = (uint8_t)((live >> i) & 1u);
-  }
-  for (int t = k_remove + r; t < n_order; t += nt) order[t] = -1;
-  if (r == 0) {
-    stats[0] = rescans;
-    stats[1] = k_remove;
-  }
-}
-
-template <int IT, int TB>
-void launch_remove(int M, const float* oT, const uint8_t* mask, const float* P0, const int32_t* C0, const float* ws, int n, int n_keep,
-                   uint8_t* keep, int64_t* order, int n_order, int32_t* stats, hipStream_t s) {
-#define BC_LAUNCH(MM) bce_remove_kernel<IT, MM, TB><<<1, TB, 0, s>>>(oT, mask, P0, C0, ws, n, n_keep, keep, order, n_order, stats)
-  if (M == 2)
-    BC_LAUNCH(2);
-  else if (M == 3)
-    BC_LAUNCH(3);
-  else if (M == 4)
-    BC_LAUNCH(4);
-  else if (M == 8)
-    BC_LAUNCH(8);
-  else
-    BC_LAUNCH(16);
-#undef BC_LAUNCH
+  evx::removal_finish<IT, TB>(live, n, k_remove, rescans, keep, order, n_order, stats);
 }
 
 inline int grid_rows(int n) { return (n + BC_ROWS - 1) / BC_ROWS; }
@@ -634,16 +579,15 @@ inline int grid_rows(int n) { return (n + BC_ROWS - 1) / BC_ROWS; }
 
 int evx_bce_max_n() { return BC_MAX_N; }
 int evx_bce_max_m() { return BC_MAX_M; }
-int evx_bce_padded_m(int m) { return m <= 2 ? 2 : m == 3 ? 3 : m == 4 ? 4 : m <= 8 ? 8 : 16; }
 int evx_bce_ws_floats() { return BC_R + 1; }
 
 void evx_bce_mask(const float* objT, int n, int M, uint8_t* mask, hipStream_t s) {
-  if (n <= 0 || M != evx_bce_padded_m(M)) return;
+  if (n <= 0 || M != evx_padded_m(M)) return;
   bce_mask_kernel<<<grid_rows(n), BC_GRID_THREADS, 0, s>>>(objT, n, M, mask);
 }
 
 void evx_bce_niche(const float* objT, int n, int M, const uint8_t* mask, float* t, float* ws, int64_t* cnt, int n_keep, hipStream_t s) {
-  if (n <= 0 || M != evx_bce_padded_m(M)) return;
+  if (n <= 0 || M != evx_padded_m(M)) return;
   bce_bounds_kernel<<<1, 256, 0, s>>>(objT, mask, n, M, ws, cnt);
   bce_niche_kernel<<<grid_rows(n), BC_GRID_THREADS, 0, s>>>(objT, mask, n, M, ws, t, cnt, n_keep);
   bce_radius_kernel<<<1, 256, 0, s>>>(t, n, cnt, ws, n_keep);
@@ -651,27 +595,18 @@ void evx_bce_niche(const float* objT, int n, int M, const uint8_t* mask, float* 
 
 void evx_bce_remove(const float* objT, int n, int M, const uint8_t* mask, const float* ws, const int64_t* cnt, float* P, int32_t* C,
                     int n_keep, uint8_t* keep, int64_t* order, int n_order, int32_t* stats, hipStream_t s) {
-  if (n <= 0 || n > BC_MAX_N || M != evx_bce_padded_m(M)) return;
+  if (n <= 0 || n > BC_MAX_N || M != evx_padded_m(M)) return;
   bce_score_kernel<<<grid_rows(n), BC_GRID_THREADS, 0, s>>>(objT, mask, n, M, ws, P, C, cnt, n_keep);
-#define BC_ARGS M, objT, mask, P, C, ws, n, n_keep, keep, order, n_order, stats, s
-  // four waves (one per SIMD) while eight rows per thread suffice, then eight waves
-  if (n <= 256)
-    launch_remove<1, 256>(BC_ARGS);
-  else if (n <= 512)
-    launch_remove<2, 256>(BC_ARGS);
-  else if (n <= 1024)
-    launch_remove<4, 256>(BC_ARGS);
-  else if (n <= 2048)
-    launch_remove<8, 256>(BC_ARGS);
-  else if (n <= 4096)
-    launch_remove<8, 512>(BC_ARGS);
-  else
-    launch_remove<16, 512>(BC_ARGS);
-#undef BC_ARGS
+  evx::dispatch_removal_shape(n, [&](auto it, auto tb) {
+    evx::dispatch_padded_m(M, [&](auto mm) {
+      constexpr int IT = decltype(it)::value, TB = decltype(tb)::value, MM = decltype(mm)::value;
+      bce_remove_kernel<IT, MM, TB><<<1, TB, 0, s>>>(objT, mask, P, C, ws, n, n_keep, keep, order, n_order, stats);
+    });
+  });
 }
 
 void evx_bce_count(const float* pcT, int N, const float* npcT, int Nn, int M, const float* ws, const int64_t* n_nd, uint8_t* out,
                    hipStream_t s) {
-  if (N <= 0 || M != evx_bce_padded_m(M)) return;
+  if (N <= 0 || M != evx_padded_m(M)) return;
   bce_count_kernel<<<grid_rows(N), BC_GRID_THREADS, 0, s>>>(pcT, N, npcT, Nn, M, ws, n_nd, out);
 }

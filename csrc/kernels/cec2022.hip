@@ -162,7 +162,7 @@ __device__ __forceinline__ float basic_row(const RowView& z, int fid, int L, int
   a = evx::wave_sum(a);
   b = evx::wave_sum(b);
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) p *= __shfl_xor(p, o, 64);
+  for (int o = 32; o > 0; o >>= 1) p *= __shfl_xor(p, o, 64);  // evx::wave_prod, written out: with the call the two large kernels change length
   switch (fid) {
     case ZAKHAROV: return a + b * b + b * b * b * b;
     case SCHAFFERF7: return a * a / (fL - 1.f) / (fL - 1.f);

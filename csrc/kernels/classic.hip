@@ -57,10 +57,7 @@ __global__ void __launch_bounds__(256) classic_kernel(const float* __restrict__ 
   }
   s0 = evx::wave_sum(s0);
   if (F == 1) s1 = evx::wave_sum(s1);
-  if (F == 4) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s1 *= __shfl_xor(s1, o, 64);
-  }
+  if (F == 4) s1 = evx::wave_prod(s1);
   if (lane == 0) {
     float f;
     if (F == 0 || F == 3 || F == 6) f = s0;

@@ -53,7 +53,7 @@
 //   ibea_truncate<8, m = 3>    86    81    0        3344
 //   ibea_truncate<8, any m>    105   106   0        3344
 // No spill: 1024 threads are four waves per SIMD, 128 VGPRs each.
-#include "evoxmi_common.h"
+#include "evoxmi_mo.h"
 
 namespace {
 
@@ -65,8 +65,7 @@ constexpr int IB_MAX_N = 8192;
 constexpr int IB_THREADS = 1024;
 constexpr int IB_WAVES = IB_THREADS / 64;
 
-// torch's amax: a NaN wins
-__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
+using evx::nan_max;
 
 __global__ void __launch_bounds__(IF_THREADS) ibea_fitness_kernel(const float* __restrict__ obj, int n, int m, float kappa,
                                                                    float* __restrict__ f, float* __restrict__ C) {
@@ -82,7 +81,7 @@ __global__ void __launch_bounds__(IF_THREADS) ibea_fitness_kernel(const float* _
     for (int i0 = 0; i0 < n; i0 += IF_TILE) {
       const int rows = min(IF_TILE, n - i0);
       __syncthreads();  // the previous tile is consumed (first pass: js is published below)
-      for (int e = tid; e < rows * m; e += IF_THREADS) is[(e / m) * ms + e % m] = obj[(int64_t)i0 * m + e];
+      evx::stage_tile<IF_THREADS>(is, obj, i0, rows, m, ms, tid);
       __syncthreads();
       if (j < n) {
         for (int il = lane; il < rows; il += 64) {
@@ -96,13 +95,9 @@ __global__ void __launch_bounds__(IF_THREADS) ibea_fitness_kernel(const float* _
         }
       }
     }
-    if (sweep == 0) {  // every lane gets the column's C (no −0 among absolute values; a NaN stays a NaN)
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) c = nan_max(c, __shfl_xor(c, o, 64));
-    }
+    if (sweep == 0) c = evx::wave_nan_max(c);  // every lane gets the column's C (no −0 among absolute values; a NaN stays a NaN)
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  sum = evx::wave_sum(sum);
   if (lane == 0 && j < n) {
     C[j] = c;
     f[j] = 1.f - sum;
@@ -119,12 +114,7 @@ constexpr unsigned long long IB_NO_KEY = ~0ull;
 // torch.argmin's order on (value, index) as one unsigned word: a NaN is below every number, −0 = +0,
 // the lower index first among equals
 __device__ __forceinline__ unsigned long long arg_key(float v, int i) {
-  uint32_t k = 0u;
-  if (v == v) {
-    const uint32_t b = __float_as_uint(v + 0.f);
-    k = (b >> 31) ? ~b : (b | 0x80000000u);
-  }
-  return ((unsigned long long)k << 32) | (uint32_t)i;
+  return evx::key64(v == v ? evx::ord_bits(v + 0.f) : 0u, (uint32_t)i);
 }
 
 // MR > 0: m == MR and the thread's objective rows live in registers; MR == 0: any m, re-read each step.

@@ -52,8 +52,7 @@
 #include <climits>
 #include <rocprim/block/block_radix_sort.hpp>
 
-#include "evoxmi_common.h"
-#include "evoxmi_launchers.h"
+#include "evoxmi_mo.h"
 
 namespace {
 
@@ -97,14 +96,6 @@ struct KnShared {
   int wcnt[KN_WAVES];
 };
 
-// the uint32 whose unsigned order is the order of the canonicalised float (NaN last, −0 = +0)
-__device__ __forceinline__ uint32_t key_image(float x) {
-  uint32_t b = __float_as_uint(x);
-  if (x != x) b = 0x7fc00000u;
-  if (x == 0.f) b = 0u;
-  return (b >> 31) ? ~b : (b | 0x80000000u);
-}
-
 __device__ __forceinline__ int64_t rank_at(const void* rank, int rank64, int p) {
   return rank64 ? ((const int64_t*)rank)[p] : (int64_t)((const int32_t*)rank)[p];
 }
@@ -118,19 +109,8 @@ __device__ __forceinline__ double uniform_d(double v) {
   return __hiloint2double(hi, lo);
 }
 
-// block-wide sum of one int per thread, broadcast; two barriers, wcnt is free again afterwards
-__device__ __forceinline__ int block_count(int v, int* wcnt) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int tot = 0;
-  for (int w = 0; w < KN_WAVES; ++w) tot += wcnt[w];
-  __syncthreads();
-  return tot;
-}
-
-// block-wide exclusive prefix of one int per thread; two barriers, wcnt is free again afterwards
+// block-wide exclusive prefix of one int per thread; two barriers, wcnt is free again afterwards.  Not evx::block_scan_excl plus a
+// barrier: with it front<16, 8> takes two SGPRs fewer and four bytes more
 __device__ __forceinline__ int block_prefix(int v, int* wcnt) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int inc = v;
@@ -293,7 +273,7 @@ __device__ __noinline__ void front(KnShared& sh, const float* __restrict__ f, in
 #pragma unroll
       for (int o = 0; o < MT; ++o)
         if (o < m) acc = acc + (double)f[(int64_t)(lo + s) * m + o] * sh.plane[o];
-      k[i] = key_image((float)acc);
+      k[i] = evx::ord_canon((float)acc);
     }
   }
   sort_t().sort(k, v, kn_storage<IT>(sh.sort));
@@ -375,7 +355,8 @@ __device__ __noinline__ void front(KnShared& sh, const float* __restrict__ f, in
       }
     }
   }
-  const int knees = block_count(__popc(kn), sh.wcnt);
+  const int knees = evx::block_sum<KN_WAVES>(__popc(kn), sh.wcnt);
+  __syncthreads();  // wcnt is free again
   if (t == 0) sh.t = (double)knees / (double)F;
   if (!is_last) return;
 
@@ -401,7 +382,7 @@ __device__ __noinline__ void front(KnShared& sh, const float* __restrict__ f, in
             acc = acc + (double)val * sh.plane[o];
           }
         }
-        const uint32_t img = key_image((float)acc);
+        const uint32_t img = evx::ord_canon((float)acc);
         k[i] = dif > 0 ? ~img : img;  // a key image is never 0: its complement stays below KN_PAD
       }
     }

@@ -93,7 +93,7 @@ template <int MT>
 __device__ __forceinline__ int count_dominators(const float* tile, int tl, const float (&own)[MT]) {
   int cnt = 0;
   for (int i = 0; i < tl; ++i) {
-    bool le = true, lt = false;
+    bool le = true, lt = false;  // the test of evx::dominates (evoxmi_mo.h), written out: with the helper the kernel grows by 24 bytes
 #pragma unroll
     for (int o = 0; o < MT; ++o) {
       const float a = tile[i * MT + o];

@@ -41,7 +41,7 @@ __global__ void __launch_bounds__(256) dominance_kernel(const float* __restrict_
   uint32_t word = 0;
   const int nb = min(32, n - 32 * w);
   for (int b = 0; b < nb; ++b) {
-    bool le = true, lt = false;
+    bool le = true, lt = false;  // the test of evx::dominates (evoxmi_mo.h), written out: its loop over a run-time m would index fj dynamically for M = 0
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       if (k < mm) {

@@ -43,7 +43,7 @@
 // 120 KiB of the CU's 160 KiB.  No spill.
 #include <rocprim/block/block_radix_sort.hpp>
 
-#include "evoxmi_common.h"
+#include "evoxmi_mo.h"
 
 namespace {
 
@@ -52,18 +52,7 @@ constexpr int NS_MAX = 8192;  // cap on n and on R
 constexpr int NS_WAVES = NS_THREADS / 64;
 constexpr int NS_NICHES = NS_MAX / NS_THREADS;  // niches owned per thread in step 5
 
-constexpr uint32_t NS_INF_KEY = 0xFF800000u;  // ordered(+inf)
-
-// float → uint32 whose unsigned order is the float order; NaN → 0, below ordered(−inf) = 0x007FFFFF
-__device__ __forceinline__ uint32_t ordered(float x) {
-  if (x != x) return 0u;
-  const uint32_t b = __float_as_uint(x);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float unordered(uint32_t k) {
-  if (k == 0u) return __int_as_float(0x7fc00000);
-  return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
+constexpr uint32_t NS_INF_KEY = 0xFF800000u;  // evx::ord_nan_first(+inf)
 
 __device__ __forceinline__ int bits_for(uint32_t vmax) {  // smallest b with vmax < 2^b, ≥ 1
   int b = 1;
@@ -83,41 +72,6 @@ struct NicheShared {
   int wsum[NS_WAVES], wsum2[NS_WAVES], red[2][NS_WAVES];
   uint32_t wave_last[NS_WAVES];
 };
-
-// exclusive block scan of a per-thread count; `total` gets the block sum
-__device__ __forceinline__ int block_scan_excl(int v, int* wsum, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int up = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += up;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < NS_WAVES; ++w) {
-    const int s = wsum[w];
-    before += w < wave ? s : 0;
-    all += s;
-  }
-  total = all;
-  return before + inc - v;
-}
-
-// block sum, one barrier: callers alternate between two `buf`s so that a buffer is rewritten
-// only after the barrier that follows its last read
-__device__ __forceinline__ int block_sum(int v, int* buf) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) buf[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int all = 0;
-#pragma unroll
-  for (int w = 0; w < NS_WAVES; ++w) all += buf[w];
-  return all;
-}
 
 template <int IT>
 __global__ void __launch_bounds__(NS_THREADS) nsga3_niche_select_kernel(const int32_t* __restrict__ rank, const int32_t* __restrict__ last_rank,
@@ -160,14 +114,14 @@ __global__ void __launch_bounds__(NS_THREADS) nsga3_niche_select_kernel(const in
         lmask |= 1u << i;
         ++nlast;
         atomicAdd(&sh.rc[g[i]], 0x10000u);
-        atomicMin(&sh.niche[g[i]], ordered(gd[i]));
+        atomicMin(&sh.niche[g[i]], evx::ord_nan_first(gd[i]));
       }
     }
   }
   // 2. Σ front → K; candidate ordinals (both scans end in a barrier that also publishes rc / big)
   int F, c;
-  block_scan_excl(nfront, sh.wsum, F);
-  int ord = block_scan_excl(nlast, sh.wsum2, c);
+  evx::block_scan_excl<NS_WAVES>(nfront, sh.wsum, F);
+  int ord = evx::block_scan_excl<NS_WAVES>(nlast, sh.wsum2, c);
   const int K = min(max(N - F, 0), c);  // uniform over the block
 
   if (K > 0) {
@@ -184,7 +138,7 @@ __global__ void __launch_bounds__(NS_THREADS) nsga3_niche_select_kernel(const in
         const int q = ord & 3;
         const uint32_t word = q == 0 ? w.x : (q == 1 ? w.y : (q == 2 ? w.z : w.w));
         // the closest member(s) of an empty niche go first, in row order
-        const bool first = (sh.rc[g[i]] & 0xFFFFu) == 0u && gd[i] == unordered(sh.niche[g[i]]);
+        const bool first = (sh.rc[g[i]] & 0xFFFFu) == 0u && gd[i] == evx::ord_nan_first_inv(sh.niche[g[i]]);
         k[i] = first ? 0u : word >> 8;  // the 24 bits of u24
         k2 = (g[i] << 1) | (first ? 0u : 1u);
         ++ord;
@@ -221,7 +175,7 @@ __global__ void __launch_bounds__(NS_THREADS) nsga3_niche_select_kernel(const in
       int s = 0;
 #pragma unroll
       for (int i = 0; i < NS_NICHES; ++i) s += min(max(mid - rj[i], 0), cj[i]);
-      s = block_sum(s, sh.red[it & 1]);
+      s = evx::block_sum<NS_WAVES>(s, sh.red[it & 1]);
       if (s < K) { lo = mid; below = s; } else hi = mid;
     }
     const int need = K - below;  // ≥ 1 niches take their candidate at level lo, lowest niche first
@@ -234,7 +188,7 @@ __global__ void __launch_bounds__(NS_THREADS) nsga3_niche_select_kernel(const in
       nown += o;
     }
     int tot;
-    int before = block_scan_excl(nown, sh.wsum, tot);  // its barrier also publishes the niche starts
+    int before = evx::block_scan_excl<NS_WAVES>(nown, sh.wsum, tot);  // its barrier also publishes the niche starts
 #pragma unroll
     for (int i = 0; i < NS_NICHES; ++i) {
       const int j = t * NS_NICHES + i;
@@ -261,7 +215,7 @@ __global__ void __launch_bounds__(NS_THREADS) nsga3_niche_select_kernel(const in
     cnt += kp;
   }
   int total;
-  int pos = block_scan_excl(cnt, sh.wsum, total);  // a barrier lies between every earlier read of wsum and here
+  int pos = evx::block_scan_excl<NS_WAVES>(cnt, sh.wsum, total);  // a barrier lies between every earlier read of wsum and here
 #pragma unroll
   for (int i = 0; i < IT; ++i) {
     if ((keep >> i) & 1u) {

@@ -11,16 +11,11 @@
 //     of the partner's run, barrier.  Runs are padded to 144 B so the ds_read_b128 lane
 //     groups hit distinct banks.
 // At NP = 16384: 55 LDS stages instead of the 105 of an all-LDS bitonic network.
-#include "evoxmi_common.h"
+#include "evoxmi_mo.h"
 #include <float.h>
 #include <rocprim/block/block_radix_sort.hpp>
 
 namespace {
-
-__device__ __forceinline__ uint32_t f2ord(float f) {
-  uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 template <int E>
 struct Run {
@@ -67,8 +62,8 @@ __global__ void __launch_bounds__(1024) bitonic_argsort_kernel(const float* __re
     unsigned long long v = 0xFFFFFFFFFFFFFFFFull;
     if (i < n) {
       const float k = keys[i];
-      uint32_t o = (k != k) ? (descending ? 0u : 0xFFFFFFFFu) : f2ord(descending ? -k : k);
-      v = ((unsigned long long)o << 32) | (uint32_t)i;
+      uint32_t o = (k != k) ? (descending ? 0u : 0xFFFFFFFFu) : evx::ord_bits(descending ? -k : k);
+      v = evx::key64(o, (uint32_t)i);
     }
     R.v[r] = v;
   }
@@ -174,8 +169,8 @@ __global__ void __launch_bounds__(1024) radix_argsort_kernel(const float* __rest
 // 16 waves per workgroup (4 per SIMD) hide the LDS latency of the broadcast chain; the
 // single-wave-per-SIMD first cut ran 53.6 µs at n = 16384 (profiles/r3_sort_microbench.log).
 __device__ __forceinline__ uint32_t ord_key(float x, bool desc) {
-  x = (x != x) ? __uint_as_float(0x7fffffffu) : (x == 0.f ? 0.f : x);  // NaN largest, -0 == +0
-  const uint32_t o = f2ord(x);
+  x = (x != x) ? __uint_as_float(0x7fffffffu) : (x == 0.f ? 0.f : x);  // NaN largest (0xFFFFFFFF; evx::ord_canon gives 0xFFC00000), -0 == +0
+  const uint32_t o = evx::ord_bits(x);
   return desc ? ~o : o;
 }
 

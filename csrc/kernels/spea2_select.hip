@@ -9,7 +9,7 @@
 // A. Fitness, a wave per row, four rows per workgroup, the other rows through LDS in tiles of 256
 // (row stride m | 1), lane l takes the rows ≡ l (mod 64) in ascending order, then a fixed xor tree:
 // the order does not depend on the row, duplicate rows get bit-equal results.
-//   spea2_fit1_kernel: S[i] = #{j : i dominates j} (all ≤ and any <; NaN compares false), nd[i] = no
+//   spea2_fit1_kernel: S[i] = #{j : i dominates j} (evx::dominates), nd[i] = no
 //     row dominates i, msk[i] = nd[i] and no NaN objective, D[i] = 1 / (sqrt(second smallest d2(i, j),
 //     j ≠ i, with multiplicity) + 2) with IEEE sqrt and division; D = NaN for a row with a NaN objective.
 //   spea2_fit2_kernel: R[j] = Σ_{i dominates j} S[i] in 32-bit integers (n ≤ 32768: below 2^30),
@@ -74,9 +74,7 @@
 //   spea2_truncate<16, 8, 512>     170   99    0        16928
 //   spea2_truncate<16, 16, 512>    193   102   0        16928
 // 256 threads are one wave per SIMD, 512 threads two (256 VGPRs each): no spill.
-#include <type_traits>
-
-#include "evoxmi_common.h"
+#include "evoxmi_mo.h"
 
 namespace {
 
@@ -103,32 +101,9 @@ __device__ __forceinline__ float d2(FA a, FB b, int m) {
 }
 
 // (d2, row) as one word whose minimum is the least d2 and, among equals, the highest row (d2 ≥ +0: its bits are ordered)
-__device__ __forceinline__ unsigned long long nn_key(float d, int row) {
-  return ((unsigned long long)__float_as_uint(d) << 32) | (uint32_t)~row;
-}
+__device__ __forceinline__ unsigned long long nn_key(float d, int row) { return evx::key64(__float_as_uint(d), (uint32_t)~row); }
 // (nn_d2, row): least nn_d2, lowest row among equals
-__device__ __forceinline__ unsigned long long arg_key(float d, int row) {
-  return ((unsigned long long)__float_as_uint(d) << 32) | (uint32_t)row;
-}
-__device__ __forceinline__ unsigned long long wave_min_key(unsigned long long k) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long q = __shfl_xor(k, o, 64);
-    k = q < k ? q : k;
-  }
-  return k;
-}
-
-// a wave-uniform word into scalar registers
-__device__ __forceinline__ unsigned long long uniform_key(unsigned long long k) {
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(k >> 32));
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)k);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
-__device__ __forceinline__ void stage_tile(float* is, const float* __restrict__ obj, int i0, int rows, int m, int ms, int tid) {
-  for (int e = tid; e < rows * m; e += SF_THREADS) is[(e / m) * ms + e % m] = obj[(int64_t)i0 * m + e];
-}
+__device__ __forceinline__ unsigned long long arg_key(float d, int row) { return evx::key64(__float_as_uint(d), (uint32_t)row); }
 
 __global__ void __launch_bounds__(SF_THREADS) spea2_fit1_kernel(const float* __restrict__ obj, int n, int m, int32_t* __restrict__ S,
                                                                  uint8_t* __restrict__ nd, uint8_t* __restrict__ msk,
@@ -150,21 +125,15 @@ __global__ void __launch_bounds__(SF_THREADS) spea2_fit1_kernel(const float* __r
   for (int j0 = 0; j0 < n; j0 += SF_TILE) {
     const int rows = min(SF_TILE, n - j0);
     __syncthreads();  // the previous tile is consumed (first pass: js is published below)
-    stage_tile(is, obj, j0, rows, m, ms, tid);
+    evx::stage_tile<SF_THREADS>(is, obj, j0, rows, m, ms, tid);
     __syncthreads();
     if (r < n) {
       for (int jl = lane; jl < rows; jl += 64) {
         const float* oj = is + jl * ms;
-        bool le = true, lt = false, ge = true, gt = false;
-        for (int k = 0; k < m; ++k) {
-          const float x = orow[k], y = oj[k];
-          le &= x <= y;
-          lt |= x < y;
-          ge &= y <= x;
-          gt |= y < x;
-        }
-        s += (le && lt) ? 1 : 0;
-        dominated |= ge && gt;
+        bool dom, domd;  // r dominates j, j dominates r
+        evx::dominates_both([&](int k) { return orow[k]; }, [&](int k) { return oj[k]; }, m, dom, domd);
+        s += dom ? 1 : 0;
+        dominated |= domd;
         if (j0 + jl != r) {
           const float d = d2([&](int k) { return orow[k]; }, [&](int k) { return oj[k]; }, m);
           if (d < a) {
@@ -178,7 +147,7 @@ __global__ void __launch_bounds__(SF_THREADS) spea2_fit1_kernel(const float* __r
     }
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
+  for (int o = 32; o > 0; o >>= 1) {  // the count and the two smallest in one tree
     s += __shfl_xor(s, o, 64);
     const float oa = __shfl_xor(a, o, 64), ob = __shfl_xor(b, o, 64);
     const float hi = fmaxf(a, oa);
@@ -216,7 +185,7 @@ __global__ void __launch_bounds__(SF_THREADS) spea2_fit2_kernel(const float* __r
   for (int i0 = 0; i0 < n; i0 += SF_TILE) {
     const int rows = min(SF_TILE, n - i0);
     __syncthreads();
-    stage_tile(is, obj, i0, rows, m, ms, tid);
+    evx::stage_tile<SF_THREADS>(is, obj, i0, rows, m, ms, tid);
     if (tid < rows) {
       ss[tid] = fit ? S[i0 + tid] : 0;
       mk[tid] = msk[i0 + tid];
@@ -225,15 +194,7 @@ __global__ void __launch_bounds__(SF_THREADS) spea2_fit2_kernel(const float* __r
     if (r < n) {
       for (int il = lane; il < rows; il += 64) {
         const float* oi = is + il * ms;
-        if (fit) {
-          bool le = true, lt = false;  // row i dominates row r
-          for (int k = 0; k < m; ++k) {
-            const float x = oi[k], y = orow[k];
-            le &= x <= y;
-            lt |= x < y;
-          }
-          racc += (le && lt) ? (uint32_t)ss[il] : 0u;
-        }
+        if (fit) racc += evx::dominates([&](int k) { return oi[k]; }, [&](int k) { return orow[k]; }, m) ? (uint32_t)ss[il] : 0u;
         if (masked && mk[il] != 0 && i0 + il != r) {
           const float d = d2([&](int k) { return orow[k]; }, [&](int k) { return oi[k]; }, m);
           if (d < inf) {
@@ -244,9 +205,8 @@ __global__ void __launch_bounds__(SF_THREADS) spea2_fit2_kernel(const float* __r
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) racc += __shfl_xor(racc, o, 64);
-  best = wave_min_key(best);
+  racc = evx::wave_sum(racc);
+  best = evx::wave_min(best);
   if (lane == 0 && r < n) {
     if (fit) {
       const float rr = (float)racc;
@@ -259,11 +219,6 @@ __global__ void __launch_bounds__(SF_THREADS) spea2_fit2_kernel(const float* __r
   }
 }
 
-struct alignas(16) SpPart {
-  unsigned long long key;
-  int cnt;
-};
-
 // oT: the objectives transposed and zero padded to (M, n); blockDim.x = TB; order has n_order entries
 template <int IT, int M, int TB>
 __global__ void __launch_bounds__(TB) spea2_truncate_kernel(const float* __restrict__ oT, const uint8_t* __restrict__ mask,
@@ -273,12 +228,12 @@ __global__ void __launch_bounds__(TB) spea2_truncate_kernel(const float* __restr
   constexpr bool REG = M <= 3;                    // the thread's objective rows live in registers
   constexpr int B = (M <= 4 && IT <= 8) ? 4 : 2;  // rescanned rows per pass
   constexpr int MO = REG ? M : 1;
-  __shared__ SpPart partF[2][SP_WAVES];
+  __shared__ evx::RemovalPart partF[2][SP_WAVES];
   __shared__ unsigned long long partP[2][SP_WAVES][B];
   __shared__ uint16_t wlist[SP_MAX_N];  // wave w: entries w·64·IT …
   __shared__ int wcount[SP_WAVES];
-  constexpr int lg = TB == 256 ? 8 : 9, nt = TB, nw = TB >> 6;
-  static_assert(TB == 256 || TB == 512, "a power of two, at most SP_THREADS");
+  using Shape = evx::RemovalShape<TB>;
+  constexpr int lg = Shape::lg, nt = Shape::nt, nw = Shape::nw;
   const int r = threadIdx.x, lane = r & 63, wave = r >> 6;
   const float inf = __uint_as_float(SP_INF);
   const unsigned long long below = (1ull << lane) - 1ull;
@@ -297,9 +252,9 @@ __global__ void __launch_bounds__(TB) spea2_truncate_kernel(const float* __restr
 #pragma unroll
     for (int k = 0; k < MO; ++k) own[i][k] = (REG && p < n) ? oT[(int64_t)k * n + p] : 0.f;
   }
-  int c = __popc(live);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  // the count and the target lookup below are the same in spea2_select.hip and bce_select.hip and stay written out: as shared
+  // helpers their unrolled wave loops are reassociated before inlining and every instantiation's code length changes
+  const int c = evx::wave_sum((int)__popc(live));
   if (lane == 0) wcount[wave] = c;
   __syncthreads();
   int count = 0;
@@ -322,23 +277,21 @@ __global__ void __launch_bounds__(TB) spea2_truncate_kernel(const float* __restr
       const int p = r + (i << lg);
       const bool on = (live >> i) & 1u;
       const bool flag = on && x >= 0 && nni[i] == x;
-      const unsigned long long bal = __ballot(flag);
-      if (flag) wlist[wave * (64 * IT) + cw + __popcll(bal & below)] = (uint16_t)p;
-      cw += __popcll(bal);
+      cw = evx::wave_append(flag, (uint16_t)p, wlist + wave * (64 * IT), cw, below);
       if (on && !flag) {
         const unsigned long long q = arg_key(nnd[i], p);
         key = q < key ? q : key;
       }
     }
-    key = wave_min_key(key);
-    if (lane == 0) partF[buf][wave] = SpPart{key, cw};
+    key = evx::wave_min(key);
+    if (lane == 0) partF[buf][wave] = evx::RemovalPart{key, cw};
     __syncthreads();
     // wave-uniform from here to the pass: readfirstlane moves the folds and the list lookups to the scalar unit
     int total = 0;
     key = SP_NO_KEY;
     for (int w = 0; w < nw; ++w) {
-      const SpPart q = partF[buf][w];
-      const unsigned long long qk = uniform_key(q.key);
+      const evx::RemovalPart q = partF[buf][w];
+      const unsigned long long qk = evx::uniform(q.key);
       total += __builtin_amdgcn_readfirstlane(q.cnt);
       key = qk < key ? qk : key;
     }
@@ -383,7 +336,7 @@ __global__ void __launch_bounds__(TB) spea2_truncate_kernel(const float* __restr
       }
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
-        const unsigned long long kb = wave_min_key(bd[b] < inf ? nn_key(bd[b], bi[b]) : SP_NO_KEY);
+        const unsigned long long kb = evx::wave_min(bd[b] < inf ? nn_key(bd[b], bi[b]) : SP_NO_KEY);
         if (lane == 0) partP[pq][wave][b] = kb;
       }
       __syncthreads();
@@ -391,7 +344,7 @@ __global__ void __launch_bounds__(TB) spea2_truncate_kernel(const float* __restr
       for (int b = 0; b < NB; ++b) {
         unsigned long long q = SP_NO_KEY;
         for (int w = 0; w < nw; ++w) {
-          const unsigned long long u = uniform_key(partP[pq][w][b]);
+          const unsigned long long u = evx::uniform(partP[pq][w][b]);
           q = u < q ? u : q;
         }
         const bool none = q == SP_NO_KEY;
@@ -423,33 +376,7 @@ __global__ void __launch_bounds__(TB) spea2_truncate_kernel(const float* __restr
     x = (int)(uint32_t)key;
   }
 
-#pragma unroll
-  for (int i = 0; i < IT; ++i) {
-    const int p = r + (i << lg);
-    if (p < n) keep[p] = (uint8_t)((live >> i) & 1u);
-  }
-  for (int t = k_remove + r; t < n_order; t += nt) order[t] = -1;
-  if (r == 0) {
-    stats[0] = rescans;
-    stats[1] = k_remove;
-  }
-}
-
-template <int IT, int TB>
-void launch_truncate(int M, const float* oT, const uint8_t* mask, const float* nn_d2, const int32_t* nn_idx, int n, int n_keep,
-                     uint8_t* keep, int64_t* order, int n_order, int32_t* stats, hipStream_t s) {
-#define SP_LAUNCH(MM) spea2_truncate_kernel<IT, MM, TB><<<1, TB, 0, s>>>(oT, mask, nn_d2, nn_idx, n, n_keep, keep, order, n_order, stats)
-  if (M == 2)
-    SP_LAUNCH(2);
-  else if (M == 3)
-    SP_LAUNCH(3);
-  else if (M == 4)
-    SP_LAUNCH(4);
-  else if (M == 8)
-    SP_LAUNCH(8);
-  else
-    SP_LAUNCH(16);
-#undef SP_LAUNCH
+  evx::removal_finish<IT, TB>(live, n, k_remove, rescans, keep, order, n_order, stats);
 }
 
 }  // namespace
@@ -457,7 +384,6 @@ void launch_truncate(int M, const float* oT, const uint8_t* mask, const float* n
 int evx_spea2_max_n() { return SP_MAX_N; }
 int evx_spea2_fitness_max_n() { return SP_FIT_MAX_N; }
 int evx_spea2_max_m() { return SP_MAX_M; }
-int evx_spea2_padded_m(int m) { return m <= 2 ? 2 : m == 3 ? 3 : m == 4 ? 4 : m <= 8 ? 8 : 16; }
 
 void evx_spea2_fitness(const float* obj, int n, int m, int32_t* S, uint8_t* nd, uint8_t* msk, float* D, float* R, float* sig,
                        float* nn_d2, int32_t* nn_idx, hipStream_t s) {
@@ -475,20 +401,11 @@ void evx_spea2_neighbours(const float* obj, int n, int m, const uint8_t* mask, f
 
 void evx_spea2_truncate(const float* objT, int n, int M, const uint8_t* mask, const float* nn_d2, const int32_t* nn_idx, int n_keep,
                         uint8_t* keep, int64_t* order, int n_order, int32_t* stats, hipStream_t s) {
-  if (n <= 0 || n > SP_MAX_N || M != evx_spea2_padded_m(M)) return;
-#define SP_ARGS M, objT, mask, nn_d2, nn_idx, n, n_keep, keep, order, n_order, stats, s
-  // four waves (one per SIMD) while eight rows per thread suffice, then eight waves
-  if (n <= 256)
-    launch_truncate<1, 256>(SP_ARGS);
-  else if (n <= 512)
-    launch_truncate<2, 256>(SP_ARGS);
-  else if (n <= 1024)
-    launch_truncate<4, 256>(SP_ARGS);
-  else if (n <= 2048)
-    launch_truncate<8, 256>(SP_ARGS);
-  else if (n <= 4096)
-    launch_truncate<8, 512>(SP_ARGS);
-  else
-    launch_truncate<16, 512>(SP_ARGS);
-#undef SP_ARGS
+  if (n <= 0 || n > SP_MAX_N || M != evx_padded_m(M)) return;
+  evx::dispatch_removal_shape(n, [&](auto it, auto tb) {
+    evx::dispatch_padded_m(M, [&](auto mm) {
+      constexpr int IT = decltype(it)::value, TB = decltype(tb)::value, MM = decltype(mm)::value;
+      spea2_truncate_kernel<IT, MM, TB><<<1, TB, 0, s>>>(objT, mask, nn_d2, nn_idx, n, n_keep, keep, order, n_order, stats);
+    });
+  });
 }

@@ -38,7 +38,7 @@
 //   sra_indicators     62    58    0        17664
 // No spill; the ranking's LDS is the two edge buffers (2 × 2 × 1024 items of 12 B) of the CU's
 // 160 KiB.
-#include "evoxmi_common.h"
+#include "evoxmi_mo.h"
 
 namespace {
 
@@ -134,9 +134,8 @@ constexpr int SI_THREADS = 64 * SI_WAVES;
 constexpr int SI_TILE = 256;          // rows q per LDS tile
 constexpr int SI_MAX_M = 16;
 
-// torch's amax / min: a NaN wins
-__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
-__device__ __forceinline__ float nan_min(float a, float b) { return (b < a || b != b) ? b : a; }
+using evx::nan_max;
+using evx::nan_min;
 
 __global__ void __launch_bounds__(SI_THREADS) sra_indicators_kernel(const float* __restrict__ obj, int n, int m, float* __restrict__ I1,
                                                                      float* __restrict__ I2) {
@@ -151,7 +150,7 @@ __global__ void __launch_bounds__(SI_THREADS) sra_indicators_kernel(const float*
   for (int q0 = 0; q0 < n; q0 += SI_TILE) {
     const int rows = min(SI_TILE, n - q0);
     __syncthreads();  // the previous tile is consumed (first pass: ps is published below)
-    for (int e = tid; e < rows * m; e += SI_THREADS) qs[(e / m) * ms + e % m] = obj[(int64_t)q0 * m + e];
+    evx::stage_tile<SI_THREADS>(qs, obj, q0, rows, m, ms, tid);
     __syncthreads();
     if (p < n) {
       for (int ql = lane; ql < rows; ql += 64) {
@@ -171,7 +170,7 @@ __global__ void __launch_bounds__(SI_THREADS) sra_indicators_kernel(const float*
     }
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
+  for (int o = 32; o > 0; o >>= 1) {  // sum and min in one tree: as evx::wave_sum and wave_nan_min the code length changes (3516 to 3488 B)
     sum += __shfl_xor(sum, o, 64);
     mn = nan_min(mn, __shfl_xor(mn, o, 64));
   }
