@@ -1044,7 +1044,7 @@ std::vector<at::Tensor> ant_rollout(const at::Tensor& W, int64_t h1, int64_t h2,
   const int64_t P = 27 * h1 + h1 + h1 * h2 + h2 + h2 * 8 + 8;
   TORCH_CHECK(W.size(1) == P, "ant_rollout: W has ", W.size(1), " columns, MLP 27-", h1, "-", h2, "-8 needs ", P);
   TORCH_CHECK(init.numel() == 29, "ant_rollout: init state must have 29 entries");
-  TORCH_CHECK((P + 32 + h1 + h2 + 8) * 4 <= 160 * 1024, "ant_rollout: MLP too large for one wave's LDS");
+  TORCH_CHECK(evx_ant_lds_bytes(P, (int)h1, (int)h2, 1) <= EVX_ANT_LDS_LIMIT, "ant_rollout: MLP too large for one wave's LDS");
   c10::DeviceGuard g(W.device());
   const int64_t N = W.size(0);
   auto ret = at::empty({N}, W.options());
@@ -1053,6 +1053,12 @@ std::vector<at::Tensor> ant_rollout(const at::Tensor& W, int64_t h1, int64_t h2,
                              steps.data_ptr<int>(), cur_stream());
   return {ret, steps};
 }
+
+// LDS of `waves` waves of the LDS-resident Ant kernel, and the limit the launcher sizes its workgroups by
+int64_t ant_lds_bytes(int64_t h1, int64_t h2, int64_t waves) {
+  return evx_ant_lds_bytes(27 * h1 + h1 + h1 * h2 + h2 + h2 * 8 + 8, (int)h1, (int)h2, (int)waves);
+}
+int64_t ant_lds_limit() { return EVX_ANT_LDS_LIMIT; }
 
 // model: the float32 table of PlanarChain.model_table(), in host memory (it travels by value in the kernel arguments)
 std::vector<at::Tensor> planar_rollout(const at::Tensor& W, int64_t h1, int64_t h2, const at::Tensor& model, const at::Tensor& init,
@@ -1978,6 +1984,8 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("pm(Tensor x, Tensor lb, Tensor ub, Tensor keys, float pro_m, float dis_m, int nm, int col0=0, int dtot=0) -> Tensor");
   m.def("nds(Tensor f, int limit=0, Tensor? err=None) -> Tensor");
   m.def("ant_rollout(Tensor W, int h1, int h2, Tensor init, int cap) -> Tensor[]");
+  m.def("ant_lds_bytes(int h1, int h2, int waves) -> int");
+  m.def("ant_lds_limit() -> int");
   m.def("planar_rollout(Tensor W, int h1, int h2, Tensor model, Tensor init, int cap) -> Tensor[]");
   m.def("stochastic_ranking(Tensor I1, Tensor I2, Tensor rnd, float pc) -> Tensor");
   m.def("moead_scan(Tensor objs, Tensor off_objs, Tensor P, Tensor W, Tensor z, int func, int nr, int update_z) -> Tensor[]");
@@ -2057,6 +2065,8 @@ TORCH_LIBRARY(evoxmi, m) {
 
 TORCH_LIBRARY_IMPL(evoxmi, CompositeExplicitAutograd, m) {
   m.impl("stochastic_ranking", &stochastic_ranking);
+  m.impl("ant_lds_bytes", &ant_lds_bytes);
+  m.impl("ant_lds_limit", &ant_lds_limit);
   m.impl("gemm_set_config", &gemm_set_config);
   m.impl("gemm_ks_set_tile", &gemm_ks_set_tile);
   m.impl("gemm_ks_set_prec", &gemm_ks_set_prec);

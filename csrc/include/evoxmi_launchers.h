@@ -199,6 +199,9 @@ void evx_de_trial(const float* P, const int32_t* idx, const float* coef, int K, 
 void evx_moead_scan(float* objs, const float* off_objs, const int32_t* P, const float* W, float* z, int32_t* owner, int N, int R,
                     int T, int M, int func, int nr, int update_z, hipStream_t s);
 void evx_ant_rollout(const float* W, int64_t P, int N, int h1, int h2, const float* init, int cap, float* ret, int* steps, hipStream_t s);
+// neuro.hip: dynamic LDS of `waves` waves of the LDS-resident Ant kernel (P weights each); a policy fits when one wave's share does
+constexpr int64_t EVX_ANT_LDS_LIMIT = 160 * 1024;
+int64_t evx_ant_lds_bytes(int64_t P, int h1, int h2, int waves);
 // planar_rollout.hip: model = the host-side float32 table of PlanarChain.model_table()
 int evx_planar_table_words();
 int evx_planar_supported(const float* model);

@@ -5,27 +5,20 @@
 //  * ant_rollout_reg_kernel (h1, h2 <= 64): weights in VGPRs, lane j = hidden unit j;
 //  * ant_rollout_kernel (larger layers): weights in LDS, lanes stride over units
 //    ((in, out) row-major, so a row read is contiguous across lanes).
-// Both integrate with the packed-f32 sub-step (art_substep_pk below); the scalar art_substep
-// stays as its readable form and as the register kernel's EVOXMI_ANT_PACKED=0 A/B path.
+// The two differ in the MLP forward only.  Both build the observation with ant_observe and run the
+// rest of the control step (torques, SUB sub-steps of ant_substep, health test, reward) in
+// ant_control.
 //
 // Physics (mirrors evoxmi/problems/neuroevolution/reinforcement_learning/envs.py:Ant, the CPU
-// oracle; constants below must match ANT / ant_derived there): the free-floating 14-DOF tree
-// (torso + 4 × thigh/shin) in generalized coordinates, integrated in momentum form.  The torso
-// state and the system's world momentum (P, L about the world origin) are quad-uniform; lane
-// quad position k owns leg k: its two hinges, their generalized momenta, and per 10 ms sub-step
-//  1. positions from the current velocities,
-//  2. knee/foot capsule-cap contacts, generalized forces, the closed-form velocity-product
-//     terms ∂T/∂q of its two links, the hinge-momentum update,
-//  3. its Schur-complement share of the 6×6 torso system (composite inertia of the pose minus
-//     b bᵀ/H of its two hinge columns, 21 entries) and of the right-hand side (6), plus its
-//     external wrench (6) — 33 quad sums (DPP) —
-//  4. a lane-uniform 6×6 LDLᵀ solve for the torso velocity, then its hinge rates by
-//     back-substitution.
+// oracle and the readable form of the integrator; constants below must match ANT / ant_derived
+// there): the free-floating 14-DOF tree (torso + 4 × thigh/shin) in generalized coordinates,
+// integrated in momentum form.  The torso state and the system's world momentum (P, L about the
+// world origin) are quad-uniform; lane quad position k owns leg k: its two hinges and their
+// generalized momenta.  The steps of a 10 ms sub-step are listed at ant_substep.
 // Waves leave the loop independently when their episode ends (sticky done), so there are no
 // block barriers after the weight load.
 #include "evoxmi_common.h"
-
-#include <cstdlib>
+#include "evoxmi_launchers.h"
 
 namespace {
 
@@ -40,21 +33,6 @@ constexpr float MTOT = M0 + 4.f * (M1 + M2);
 constexpr int SUB = 5;
 __constant__ float LEG_ANG[4] = {0.7854f, 2.3562f, 3.9270f, 5.4978f};
 __constant__ float ANK_SGN[4] = {1.f, -1.f, -1.f, 1.f};
-
-struct AntBody {  // quad-uniform: torso pose / world velocities and the system's world momentum
-  float p[3], q[4], v[3], w[3], P[3], L[3];
-};
-struct AntLeg {  // per lane: this lane's leg (raw joint coordinates)
-  float hq, aq, hqd, aqd, pih, pik;
-  float hx, hy, sg, base;
-};
-
-__device__ __forceinline__ void cross(const float* a, const float* b, float* o) {
-  o[0] = a[1] * b[2] - a[2] * b[1];
-  o[1] = a[2] * b[0] - a[0] * b[2];
-  o[2] = a[0] * b[1] - a[1] * b[0];
-}
-__device__ __forceinline__ float dot3(const float* a, const float* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
 __device__ __forceinline__ float quad_sum(float v) {
   // bound_ctrl DPP movs (no "old" operand to initialise): both stages fuse into v_add_f32_dpp
@@ -73,6 +51,25 @@ __device__ __forceinline__ float rl(float v, int l) {
 __device__ __forceinline__ float sel4(int k, float a, float b, float c, float d) {
   return k == 0 ? a : (k == 1 ? b : (k == 2 ? c : d));
 }
+
+// ---------------------------------------------------------------- initial state (scalar, once per episode)
+// load_body reads the reset state and init_momenta turns its velocities into the momenta the
+// integrator carries (Ant.initial_momenta in envs.py).  This is plain scalar code, not a second
+// integrator: it runs once per episode, then pk_from hands the state to ant_substep.
+struct AntBody {  // quad-uniform: torso pose / world velocities and the system's world momentum
+  float p[3], q[4], v[3], w[3], P[3], L[3];
+};
+struct AntLeg {  // per lane: this lane's leg (raw joint coordinates)
+  float hq, aq, hqd, aqd, pih, pik;
+  float hx, hy, sg, base;
+};
+
+__device__ __forceinline__ void cross(const float* a, const float* b, float* o) {
+  o[0] = a[1] * b[2] - a[2] * b[1];
+  o[1] = a[2] * b[0] - a[0] * b[2];
+  o[2] = a[0] * b[1] - a[1] * b[0];
+}
+__device__ __forceinline__ float dot3(const float* a, const float* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
 // rotation matrix of a unit quaternion (row-major): R v and Rᵀ v then cost 9 FMAs each
 __device__ __forceinline__ void quat_mat(const float* q, float* R) {
@@ -169,111 +166,6 @@ __device__ __forceinline__ void leg_vel(const LegPose& k, const float* vB, const
   }
 }
 
-// penalty contact of a capsule end-cap sphere at torso-frame point x with torso-frame velocity
-// vb: the contact force in the torso frame
-__device__ __forceinline__ void cap_contact(const AntBody& s, const float* R, const float* x, const float* vb, float* fb) {
-  float vw[3];
-  mrot(R, vb, vw);
-  const float pz = s.p[2] + R[6] * x[0] + R[7] * x[1] + R[8] * x[2];
-  const float pen = fmaxf(RAD - pz, 0.f);
-  const float fn = fmaxf(KC * pen - CC * vw[2] * (pen > 0.f ? 1.f : 0.f), 0.f);
-  const float ivn = rsqrtf(vw[0] * vw[0] + vw[1] * vw[1] + EPSV * EPSV);
-  const float f[3] = {-MU * fn * vw[0] * ivn, -MU * fn * vw[1] * ivn, fn};
-  mrot_t(R, f, fb);
-}
-
-// 6×6 SPD solve A x = b (A symmetric, upper part used; fully unrolled, lane-uniform)
-__device__ __forceinline__ void solve6(float (&A)[6][6], float (&b)[6], float (&x)[6]) {
-  float inv[6];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    inv[k] = __builtin_amdgcn_rcpf(A[k][k]);
-#pragma unroll
-    for (int i = k + 1; i < 6; ++i) {
-      const float f = A[k][i] * inv[k];
-#pragma unroll
-      for (int j = i; j < 6; ++j) A[i][j] -= f * A[k][j];
-      b[i] -= f * b[k];
-    }
-  }
-#pragma unroll
-  for (int k = 5; k >= 0; --k) {
-    float r = b[k];
-#pragma unroll
-    for (int j = k + 1; j < 6; ++j) r -= A[k][j] * x[j];
-    x[k] = r * inv[k];
-  }
-}
-
-// velocities from the momenta at the current pose (Schur complement over the legs)
-__device__ __forceinline__ void solve_velocities(AntBody& s, AntLeg& g, const LegPose& k, const float* R) {
-  float bphi[6], ba[6], Hphi, Ha;
-  leg_columns(k, bphi, ba, Hphi, Ha);
-  const float iHp = __builtin_amdgcn_rcpf(Hphi), iHa = __builtin_amdgcn_rcpf(Ha);
-  const float pphi = g.pih, pa = g.pik * g.sg;
-  // this leg's composite inertia about the torso origin (thigh along er, shin along d)
-  float S1[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) S1[i] = M1 * k.c1[i] + M2 * k.c2[i];
-  const float n1 = M1 * dot3(k.c1, k.c1) + M2 * dot3(k.c2, k.c2) + IP1 + IP2;
-  float sp[6], sa_[6];  // the hinge columns scaled by 1/H
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    sp[i] = bphi[i] * iHp;
-    sa_[i] = ba[i] * iHa;
-  }
-  float A[6][6], b[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-#pragma unroll
-    for (int j = i; j < 6; ++j) {
-      float m = 0.f;
-      if (i >= 3 && j >= 3) {
-        const int r = i - 3, c = j - 3;
-        m = (IA1 - IP1) * k.er[r] * k.er[c] + (IA2 - IP2) * k.d[r] * k.d[c] - M1 * k.c1[r] * k.c1[c] - M2 * k.c2[r] * k.c2[c];
-        if (r == c) m += n1;
-      } else if (i < 3 && j >= 3) {  // −[S1]×
-        const int r = i, c = j - 3;
-        if (r == 0 && c == 1) m = S1[2];
-        if (r == 0 && c == 2) m = -S1[1];
-        if (r == 1 && c == 0) m = -S1[2];
-        if (r == 1 && c == 2) m = S1[0];
-        if (r == 2 && c == 0) m = S1[1];
-        if (r == 2 && c == 1) m = -S1[0];
-      }
-      A[i][j] = quad_sum(m - sp[i] * bphi[j] - sa_[i] * ba[j]);
-    }
-    b[i] = quad_sum(-sp[i] * pphi - sa_[i] * pa);
-  }
-  A[0][0] += MTOT; A[1][1] += MTOT; A[2][2] += MTOT;
-  A[3][3] += I0; A[4][4] += I0; A[5][5] += I0;
-  {
-    float hP[3], pxP[3], Lo[3], hL[3];
-    mrot_t(R, s.P, hP);
-    cross(s.p, s.P, pxP);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) Lo[i] = s.L[i] - pxP[i];
-    mrot_t(R, Lo, hL);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      b[i] += hP[i];
-      b[3 + i] += hL[i];
-    }
-  }
-  float u[6];
-  solve6(A, b, u);
-  float bu = 0.f, au = 0.f;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    bu += bphi[i] * u[i];
-    au += ba[i] * u[i];
-  }
-  g.hqd = (pphi - bu) * iHp;
-  g.aqd = g.sg * (pa - au) * iHa;
-  mrot(R, u, s.v);
-  mrot(R, u + 3, s.w);
-}
-
 // momenta of the initial state (Ant.initial_momenta in envs.py)
 __device__ __forceinline__ void init_momenta(AntBody& s, AntLeg& g) {
   float R[9];
@@ -312,122 +204,6 @@ __device__ __forceinline__ void init_momenta(AntBody& s, AntLeg& g) {
   g.pik = g.sg * pa;
 }
 
-// One 10 ms sub-step (Ant._substep in envs.py); th / ta: this lane's leg torques
-__device__ __forceinline__ void art_substep(AntBody& s, AntLeg& g, float th, float ta) {
-  // 1. positions with the current velocities
-#pragma unroll
-  for (int i = 0; i < 3; ++i) s.p[i] += DT * s.v[i];
-  {
-    const float w = s.q[0], x = s.q[1], y = s.q[2], z = s.q[3];
-    const float ox = s.w[0], oy = s.w[1], oz = s.w[2];
-    float nq[4] = {w + DT * 0.5f * (-ox * x - oy * y - oz * z), x + DT * 0.5f * (ox * w + oy * z - oz * y),
-                   y + DT * 0.5f * (oy * w + oz * x - ox * z), z + DT * 0.5f * (oz * w + ox * y - oy * x)};
-    const float in = rsqrtf(nq[0] * nq[0] + nq[1] * nq[1] + nq[2] * nq[2] + nq[3] * nq[3]);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) s.q[c] = nq[c] * in;
-  }
-  g.hq += DT * g.hqd;
-  g.aq += DT * g.aqd;
-  // 2. forces and velocity-product terms at the new pose, old velocities
-  float R[9];
-  quat_mat(s.q, R);
-  LegPose k;
-  leg_pose(g, k);
-  float vB[3], wB[3];
-  mrot_t(R, s.v, vB);
-  mrot_t(R, s.w, wB);
-  const float phid = g.hqd, ad = g.aqd * g.sg;
-  float V1[3], V2[3], O2[3], IO1[3], IO2[3];
-  leg_vel(k, vB, wB, phid, ad, V1, V2, O2, IO1, IO2);
-  float fK[3], fF[3];
-  {
-    float a[3], vk[3], vf[3];
-    cross(wB, k.K, a);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) vk[i] = vB[i] + a[i] + L1 * phid * k.ep[i];
-    cross(wB, k.F, a);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) vf[i] = vB[i] + a[i] + L1 * phid * k.ep[i] + L2 * (phid * k.ca * k.ep[i] + ad * k.dd[i]);
-    cap_contact(s, R, k.K, vk, fK);
-    cap_contact(s, R, k.F, vf, fF);
-  }
-  const float gB[3] = {-GRAV * R[6], -GRAV * R[7], -GRAV * R[8]};
-  // contact moments about the hip, the legs' first mass moment S1 = m1 c1 + m2 c2
-  float Tk[3], S1[3], fs[3];
-  {
-    float kh[3] = {k.K[0] - g.hx, k.K[1] - g.hy, k.K[2]}, fh[3] = {k.F[0] - g.hx, k.F[1] - g.hy, k.F[2]}, a[3], b[3];
-    cross(kh, fK, a);
-    cross(fh, fF, b);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      Tk[i] = a[i] + b[i];
-      S1[i] = M1 * k.c1[i] + M2 * k.c2[i];
-      fs[i] = fK[i] + fF[i];
-    }
-  }
-  // e_z · [(S1 − m_leg h) × g + Tk];  e_p · [(c2 − K) × m2 g + (F − K) × fF] = L2 δd · (½ m2 g + fF)
-  const float Qphi = (S1[0] - (M1 + M2) * g.hx) * gB[1] - (S1[1] - (M1 + M2) * g.hy) * gB[0] + Tk[2];
-  const float Qa = L2 * (k.dd[0] * (0.5f * M2 * gB[0] + fF[0]) + k.dd[1] * (0.5f * M2 * gB[1] + fF[1]) + k.dd[2] * (0.5f * M2 * gB[2] + fF[2]));
-  float dphi, da;
-  {
-    float r1[3], r2[3], q1[3], q2[3];
-    const float wz = wB[2];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      r1[i] = 0.5f * L1 * k.er[i];
-      r2[i] = L1 * k.er[i] + 0.5f * L2 * k.d[i];
-    }
-    const float wr1 = dot3(wB, r1), wr2 = dot3(wB, r2);
-    const float a2 = (L1 + 0.5f * L2 * k.ca) * phid, b2 = 0.5f * L2 * ad * k.sa;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      q1[i] = -r1[i] * wz - 0.5f * L1 * phid * k.er[i];
-      q2[i] = -r2[i] * wz - a2 * k.er[i] - b2 * k.ep[i];
-    }
-    q1[2] += wr1;
-    q2[2] += wr2;
-    const float IOx = IO1[0] + IO2[0], IOy = IO1[1] + IO2[1];
-    dphi = M1 * dot3(V1, q1) + M2 * dot3(V2, q2) - (wB[0] * IOy - wB[1] * IOx);
-    float dc2[3];
-    cross(wB, k.s2, dc2);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) dc2[i] += 0.5f * L2 * (-phid * k.sa * k.ep[i] - ad * k.d[i]);
-    da = M2 * dot3(V2, dc2) + (IA2 - IP2) * dot3(O2, k.dd) * dot3(O2, k.d);
-  }
-  const float mag = g.aq * g.sg;
-  const float vh = fmaxf(HIP_LO - g.hq, 0.f) - fmaxf(g.hq - HIP_HI, 0.f);
-  const float va = fmaxf(ANK_LO - mag, 0.f) - fmaxf(mag - ANK_HI, 0.f);
-  g.pih += DT * (th - JD * g.hqd + LIMK * vh + Qphi + dphi);
-  g.pik += DT * (ta - JD * g.aqd + LIMK * va * g.sg + g.sg * (Qa + da));
-  // external wrench on the system: contacts and the legs' weight about the torso origin
-  // (Tk + h × fs + S1 × g per leg)
-  {
-    float X[6], a[3], b[3];
-    const float h[3] = {g.hx, g.hy, 0.f};
-    cross(h, fs, a);
-    cross(S1, gB, b);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      X[i] = quad_sum(fs[i]);
-      X[3 + i] = quad_sum(Tk[i] + a[i] + b[i]);
-    }
-    float FW[3], TW[3], pxF[3];
-    mrot(R, X, FW);
-    FW[0] -= LDAMP * s.v[0];
-    FW[1] -= LDAMP * s.v[1];
-    FW[2] += -MTOT * GRAV - LDAMP * s.v[2];
-    mrot(R, X + 3, TW);
-    cross(s.p, FW, pxF);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      s.P[i] += DT * FW[i];
-      s.L[i] += DT * (TW[i] + pxF[i] - ADAMP * s.w[i]);
-    }
-  }
-  // 3. velocities from the momenta at the new pose
-  solve_velocities(s, g, k, R);
-}
-
 __device__ __forceinline__ void load_body(AntBody& s, AntLeg& g, const float* __restrict__ init, int leg) {
   for (int i = 0; i < 3; ++i) s.p[i] = init[i];
   for (int i = 0; i < 4; ++i) s.q[i] = init[3 + i];
@@ -444,14 +220,24 @@ __device__ __forceinline__ void load_body(AntBody& s, AntLeg& g, const float* __
   init_momenta(s, g);
 }
 
-// ---------------------------------------------------------------- packed-f32 sub-step
-// The same sub-step written on register pairs for the lone-wave regime (pop ≤ #SIMDs: one wave
-// owns its SIMD and the step is VALU-issue bound).  A v_pk_fma_f32 issues at about the cost of a
+// ---------------------------------------------------------------- the sub-step (packed f32)
+// One 10 ms sub-step of the articulated body (Ant._substep in envs.py).  Per lane, for its leg:
+//  1. positions from the current velocities,
+//  2. knee/foot capsule-cap contacts, generalized forces, the closed-form velocity-product
+//     terms ∂T/∂q of its two links, the hinge-momentum update,
+//  3. its Schur-complement share of the 6×6 torso system (composite inertia of the pose minus
+//     b bᵀ/H of its two hinge columns, 21 entries) and of the right-hand side (6), plus its
+//     external wrench (6) — 33 quad sums (DPP) —
+//  4. a lane-uniform 6×6 LDLᵀ solve for the torso velocity, then its hinge rates by
+//     back-substitution.
+// It is written on register pairs because in the lone-wave regime (pop ≤ #SIMDs: one wave owns
+// its SIMD) the step is VALU-issue bound.  A v_pk_fma_f32 issues at about the cost of a
 // v_fma_f32 (tools/probe_pk_f32.hip) but does two FMAs, so every 3-vector keeps (x, y) in an
 // aligned pair and z apart, the two hinges of a leg share pairs (hip, signed ankle), and the
-// rotation R is held both as column pairs (R v) and row pairs (Rᵀ v).  The compiler's SLP
-// vectoriser found pairs too but paid ~400 v_mov for them (1139 vs 913 instructions, 9.8 vs
-// 8.3 ms at pop 1024, profiles/r5_ant_packed.txt); the swizzles here ride on op_sel / neg
+// rotation R is held both as column pairs (R v) and row pairs (Rᵀ v).  Scalar code is 913
+// instructions per sub-step and 8.3 ms at pop 1024; the compiler's SLP vectoriser finds pairs in
+// it but pays ~400 v_mov for them (1139 instructions, 9.8 ms; profiles/r5_ant_packed.txt), which
+// is why this file is built with -fno-slp-vectorize.  The swizzles here ride on op_sel / neg
 // modifiers of hand-written VOP3P instructions instead.  Signed ankle variables (a = sg·aq,
 // its rate and momentum) make every leg's equations identical; sg appears only at the
 // observation and the actuator.
@@ -573,8 +359,9 @@ __device__ __forceinline__ void pk_from(const AntBody& s, const AntLeg& g, PkBod
   l.base = g.base;
 }
 
-// cap_contact on pairs: contact force (torso frame) on a capsule end-cap at torso point x moving with vb
-__device__ __forceinline__ V3 pk_contact(const PkBody& s, const PkRot& R, const V3& x, const V3& vb) {
+// penalty contact of a capsule end-cap sphere at torso-frame point x moving with torso-frame velocity vb:
+// the contact force in the torso frame
+__device__ __forceinline__ V3 ant_contact(const PkBody& s, const PkRot& R, const V3& x, const V3& vb) {
   const V3 vw = rmul(R, vb);
   const float pz = s.p.z + R.r6 * x.xy.x + R.r7 * x.xy.y + R.r8 * x.z;
   const float pen = fmaxf(RAD - pz, 0.f);
@@ -583,8 +370,8 @@ __device__ __forceinline__ V3 pk_contact(const PkBody& s, const PkRot& R, const 
   return rtmul(R, mk3(vw.xy * (-MU * fn * ivn), fn));
 }
 
-// Ant._substep on pairs; tq = (hip torque, sg · ankle torque)
-__device__ __forceinline__ void art_substep_pk(PkBody& s, PkLeg& g, f2 tq) {
+// tq = (hip torque, sg · ankle torque) of this lane's leg
+__device__ __forceinline__ void ant_substep(PkBody& s, PkLeg& g, f2 tq) {
   // 1. positions with the current velocities
   s.p.xy += DT * s.v.xy;
   s.p.z += DT * s.v.z;
@@ -613,7 +400,7 @@ __device__ __forceinline__ void art_substep_pk(PkBody& s, PkLeg& g, f2 tq) {
   const f2 t1 = (0.5f * L1) * ep, t2 = r2c * ep;  // z = 0
   const V3 s2 = mk3((0.5f * L2) * dd.xy, -0.5f * L2 * ca);
   const float phid = g.rate.x, ad = g.rate.y;
-  // link velocities and rod-inertia angular momenta (leg_vel)
+  // link velocities (torso frame) and the rod-inertia angular momenta
   const V3 a1 = crs_b0(wB, c1), a2 = crs(wB, c2);
   const V3 V1 = mk3(vB.xy + a1.xy + t1 * phid, vB.z + a1.z);
   const V3 V2 = mk3(vB.xy + a2.xy + t2 * phid + s2.xy * ad, vB.z + a2.z + s2.z * ad);
@@ -627,7 +414,7 @@ __device__ __forceinline__ void art_substep_pk(PkBody& s, PkLeg& g, f2 tq) {
   const f2 vlin = vB.xy + (L1 * phid) * ep;
   const V3 vk = mk3(vlin + wK.xy, vB.z + wK.z);
   const V3 vf = mk3(vlin + wF.xy + (L2 * phid * ca) * ep + (L2 * ad) * dd.xy, vB.z + wF.z + L2 * ad * dd.z);
-  const V3 fK = pk_contact(s, R, mk3(K, 0.f), vk), fF = pk_contact(s, R, F, vf);
+  const V3 fK = ant_contact(s, R, mk3(K, 0.f), vk), fF = ant_contact(s, R, F, vf);
   const V3 gB = mk3(R.w2 * (-GRAV), -GRAV * R.r8);
   // contact moments about the hip, the legs' first mass moment S1 = m1 c1 + m2 c2
   const f2 kh = L1 * er;  // K − h (z = 0)
@@ -671,10 +458,10 @@ __device__ __forceinline__ void art_substep_pk(PkBody& s, PkLeg& g, f2 tq) {
     s.L.xy += DT * (TW.xy + pxF.xy - ADAMP * s.w.xy);
     s.L.z += DT * (TW.z + pxF.z - ADAMP * s.w.z);
   }
-  // 3. velocities from the momenta at the new pose (solve_velocities), in the permuted basis
+  // 3. velocities from the momenta at the new pose (Schur complement over the legs), in the permuted basis
   // (lin x, lin y | ang x, ang y | lin z, ang z) so that every pair of the 6-vectors and of the
   // Schur-complement rows is an (x, y) pair of the 3-vector algebra.
-  // hinge columns of M_bj (leg_columns): bphi = (M1 t1 + M2 t2 | M1 c1×t1 + M2 c2×t2 − cz d + (IP1+IP2) e_z),
+  // hinge columns of M_bj (linear | angular about the torso origin): bphi = (M1 t1 + M2 t2 | M1 c1×t1 + M2 c2×t2 − cz d + (IP1+IP2) e_z),
   // ba = (M2 s2 | M2 c2×s2 + IP2 ep)
   const float cz = (IA2 - IP2) * sa;
   const V3 x2 = crs_b0(c2, t2), x3 = crs(c2, s2);
@@ -748,7 +535,7 @@ __device__ __forceinline__ void art_substep_pk(PkBody& s, PkLeg& g, f2 tq) {
     b[3] += hL.xy.y; b[4] += hP.z; b[5] += hL.z;
   }
   f2 bv[3] = {f2{b[0], b[1]}, f2{b[2], b[3]}, f2{b[4], b[5]}};
-  // Gaussian elimination on the upper triangle (solve6), the row updates as pair FMAs
+  // 4. Gaussian elimination on the upper triangle (fully unrolled, lane-uniform), the row updates as pair FMAs
   float inv[6], u[6];
 #pragma unroll
   for (int k = 0; k < 6; ++k) {
@@ -782,6 +569,62 @@ __device__ __forceinline__ void art_substep_pk(PkBody& s, PkLeg& g, f2 tq) {
   s.w = rmul(R, mk3(U1, u[5]));
 }
 
+// ---------------------------------------------------------------- the control step around the MLP
+// The 27 observations (Ant.observe in envs.py): torso height, quaternion, the 8 joint angles, torso
+// velocities, the 8 joint rates.  The body part is lane-uniform; the joints come from the leg-owning
+// lanes 0-3 by v_readlane, the ankle with its sign put back.
+__device__ __forceinline__ void ant_observe(const PkBody& s, const PkLeg& g, float (&o)[27]) {
+  o[0] = s.p.z;
+  o[1] = s.qwx.x;
+  o[2] = s.qwx.y;
+  o[3] = s.qyz.x;
+  o[4] = s.qyz.y;
+  const float aq = g.ang.y * g.sg, aqd = g.rate.y * g.sg;
+#pragma unroll
+  for (int l = 0; l < 4; ++l) {
+    o[5 + 2 * l] = rl(g.ang.x, l);
+    o[6 + 2 * l] = rl(aq, l);
+    o[19 + 2 * l] = rl(g.rate.x, l);
+    o[20 + 2 * l] = rl(aqd, l);
+  }
+  o[13] = s.v.xy.x;
+  o[14] = s.v.xy.y;
+  o[15] = s.v.z;
+  o[16] = s.w.xy.x;
+  o[17] = s.w.xy.y;
+  o[18] = s.w.z;
+}
+
+// From the 8 clamped actions: this lane's leg torques, SUB sub-steps, the health test and the reward.
+// Returns whether the episode goes on; the terminating step earns nothing (sticky done).
+// ROLLED puts `#pragma unroll 1` on the sub-step loop (the register kernel); without it the compiler
+// decides (the LDS kernel).  Today both come out as a loop of one 642-instruction sub-step.
+template <bool ROLLED>
+__device__ __forceinline__ bool ant_control(PkBody& s, PkLeg& g, int leg, const float (&act)[8], float& total) {
+  float tau[8], csum = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    tau[j] = GEAR * act[j];
+    csum += act[j] * act[j];
+  }
+  const float x0 = s.p.xy.x;
+  const float th = sel4(leg, tau[0], tau[2], tau[4], tau[6]), ta = sel4(leg, tau[1], tau[3], tau[5], tau[7]);
+  const f2 tq = f2{th, ta * g.sg};
+  if constexpr (ROLLED) {
+#pragma unroll 1
+    for (int k = 0; k < SUB; ++k) ant_substep(s, g, tq);
+  } else {
+    for (int k = 0; k < SUB; ++k) ant_substep(s, g, tq);
+  }
+  const bool healthy = (s.p.z >= 0.2f) && (s.p.z <= 1.0f);
+  if (!healthy) return false;
+  total += (s.p.xy.x - x0) * (1.f / (DT * SUB)) + 1.f - 0.5f * csum;
+  return true;
+}
+
+// words of LDS one wave of ant_rollout_kernel uses: weights (P) | act0 (32) | act1 (h1) | act2 (h2) | act3 (8)
+__host__ __device__ constexpr int64_t ant_lds_words(int64_t P, int h1, int h2) { return P + 32 + h1 + h2 + 8; }
+
 // layer sizes: in = 27, hidden h1, h2 (any, ≤ 256), out = 8; tanh everywhere
 __global__ void __launch_bounds__(256) ant_rollout_kernel(const float* __restrict__ W, int64_t P, int N, int h1, int h2,
                                                           const float* __restrict__ init, int cap, float* __restrict__ ret,
@@ -789,9 +632,7 @@ __global__ void __launch_bounds__(256) ant_rollout_kernel(const float* __restric
   extern __shared__ float smem[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int ind = blockIdx.x * waves_per_block + wv;
-  // per-wave LDS: weights (P) | act0 (32) | act1 (h1) | act2 (h2)
-  const int64_t per = P + 32 + h1 + h2 + 8;
-  float* wl = smem + wv * per;
+  float* wl = smem + wv * ant_lds_words(P, h1, h2);
   float* a0 = wl + P;
   float* a1 = a0 + 32;
   float* a2 = a1 + h1;
@@ -809,39 +650,17 @@ __global__ void __launch_bounds__(256) ant_rollout_kernel(const float* __restric
   AntLeg g0;
   const int leg = lane & 3;
   load_body(s0, g0, init, leg);
-  // the packed-f32 sub-step (art_substep_pk), as in the register-resident kernel
   PkBody s;
   PkLeg g;
   pk_from(s0, g0, s, g);
   float total = 0.f;
   int t = 0;
   for (; t < cap; ++t) {
-    // observation → LDS (the joints come from the leg-owning lanes 0-3)
-    float jq[8], jqd[8];
-    const float aq = g.ang.y * g.sg, aqd = g.rate.y * g.sg;
-#pragma unroll
-    for (int l = 0; l < 4; ++l) {
-      jq[2 * l] = rl(g.ang.x, l);
-      jq[2 * l + 1] = rl(aq, l);
-      jqd[2 * l] = rl(g.rate.x, l);
-      jqd[2 * l + 1] = rl(aqd, l);
-    }
+    float o[27];
+    ant_observe(s, g, o);
     if (lane == 0) {
-      a0[0] = s.p.z;
-      a0[1] = s.qwx.x;
-      a0[2] = s.qwx.y;
-      a0[3] = s.qyz.x;
-      a0[4] = s.qyz.y;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) a0[5 + i] = jq[i];
-      a0[13] = s.v.xy.x;
-      a0[14] = s.v.xy.y;
-      a0[15] = s.v.z;
-      a0[16] = s.w.xy.x;
-      a0[17] = s.w.xy.y;
-      a0[18] = s.w.z;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) a0[19 + i] = jqd[i];
+      for (int i = 0; i < 27; ++i) a0[i] = o[i];
     }
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -863,21 +682,11 @@ __global__ void __launch_bounds__(256) ant_rollout_kernel(const float* __restric
       a3[lane] = tanhf(acc);
     }
     __builtin_amdgcn_wave_barrier();
-    float act[8], tau[8], csum = 0.f;
+    float act[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      act[j] = fminf(fmaxf(a3[j], -1.f), 1.f);
-      tau[j] = GEAR * act[j];
-      csum += act[j] * act[j];
-    }
+    for (int j = 0; j < 8; ++j) act[j] = fminf(fmaxf(a3[j], -1.f), 1.f);
     __builtin_amdgcn_wave_barrier();  // a0..a3 are rewritten next step
-    const float x0 = s.p.xy.x;
-    const float th = sel4(leg, tau[0], tau[2], tau[4], tau[6]), ta = sel4(leg, tau[1], tau[3], tau[5], tau[7]);
-    const f2 tq = f2{th, ta * g.sg};
-    for (int k = 0; k < SUB; ++k) art_substep_pk(s, g, tq);
-    const bool healthy = (s.p.z >= 0.2f) && (s.p.z <= 1.0f);
-    if (!healthy) break;  // sticky done: the terminating step earns nothing
-    total += (s.p.xy.x - x0) * (1.f / (DT * SUB)) + 1.f - 0.5f * csum;
+    if (!ant_control<false>(s, g, leg, act, total)) break;
   }
   if (lane == 0) {
     ret[ind] = total;
@@ -918,21 +727,23 @@ constexpr int ANT_WAVES = 4;
 
 typedef float ant_f4 __attribute__((ext_vector_type(4)));
 
-// KM > 0: layer 2's first KM inputs go through the matrix cores while the VALU takes the rest, both
+// Layer 2's first ANT_L2_MFMA inputs go through the matrix cores while the VALU takes the rest, both
 // issued from the same wave so the two pipes run concurrently.  v_mfma_f32_4x4x1_16b_f32 with
 // A = the lane's weight (block b = output units 4b..4b+3) and B = a1[k] in all four columns: every
 // block column holds the same four sums, so c[lane & 3] is unit `lane` whatever the column order.
 // tools/k15_mfma_probe.hip measured the isolated 64x64 layer (one wave): VALU 1100 cycles, MFMA-only
 // 4x4x1 1078, 16x16x4 with the vector padded to 16 columns 2755, split 16 / 48 907
-// (profiles/r3_k15_mfma_probe.log).
-template <int KM, bool PK>
+// (profiles/r3_k15_mfma_probe.log).  16 is the split that is fastest for the isolated layer; inside
+// the rollout every split is within noise (1000-step latency 8.63 ms VALU only, 8.70 at 16, 8.67 at
+// 32; profiles/r3_k15_ant_l2_mfma_ab.txt) because layer 2 is ≈5 % of a control step.
+constexpr int ANT_L2_MFMA = 16;
+
 __global__ void __launch_bounds__(64 * ANT_WAVES, 2) ant_rollout_reg_kernel(const float* __restrict__ W, int64_t P, int N, int h1, int h2,
                                                                           const float* __restrict__ init, int cap, float* __restrict__ ret,
-                                                                          int* __restrict__ steps_out, int trace) {
+                                                                          int* __restrict__ steps_out) {
   __shared__ float a1s_all[ANT_WAVES][64];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   float* a1s = a1s_all[wv];
-  const unsigned long long t_start = trace ? __builtin_amdgcn_s_memtime() : 0ull;
   const int ind = blockIdx.x * ANT_WAVES + wv;  // waves never synchronise with each other
   if (ind >= N) return;
   const float* W1 = W + (int64_t)ind * P;
@@ -956,52 +767,17 @@ __global__ void __launch_bounds__(64 * ANT_WAVES, 2) ant_rollout_reg_kernel(cons
   }
   const bool hb5 = lane & 32, hb4 = lane & 16, hb3 = lane & 8;
   const int leg = lane & 3;
-  AntBody s;
-  AntLeg g;
-  load_body(s, g, init, leg);
-  PkBody pb;
-  PkLeg pl;
-  if constexpr (PK) pk_from(s, g, pb, pl);
+  AntBody s0;
+  AntLeg g0;
+  load_body(s0, g0, init, leg);
+  PkBody s;
+  PkLeg g;
+  pk_from(s0, g0, s, g);
   float total = 0.f;
   int t = 0;
   for (; t < cap; ++t) {
     float o[27];
-    if constexpr (PK) {
-      o[0] = pb.p.z;
-      o[1] = pb.qwx.x;
-      o[2] = pb.qwx.y;
-      o[3] = pb.qyz.x;
-      o[4] = pb.qyz.y;
-      const float aq = pl.ang.y * pl.sg, aqd = pl.rate.y * pl.sg;
-#pragma unroll
-      for (int l = 0; l < 4; ++l) {
-        o[5 + 2 * l] = rl(pl.ang.x, l);
-        o[6 + 2 * l] = rl(aq, l);
-        o[19 + 2 * l] = rl(pl.rate.x, l);
-        o[20 + 2 * l] = rl(aqd, l);
-      }
-      o[13] = pb.v.xy.x;
-      o[14] = pb.v.xy.y;
-      o[15] = pb.v.z;
-      o[16] = pb.w.xy.x;
-      o[17] = pb.w.xy.y;
-      o[18] = pb.w.z;
-    } else {
-      o[0] = s.p[2];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) o[1 + i] = s.q[i];
-#pragma unroll
-      for (int l = 0; l < 4; ++l) {
-        o[5 + 2 * l] = rl(g.hq, l);
-        o[6 + 2 * l] = rl(g.aq, l);
-        o[19 + 2 * l] = rl(g.hqd, l);
-        o[20 + 2 * l] = rl(g.aqd, l);
-      }
-#pragma unroll
-      for (int i = 0; i < 3; ++i) o[13 + i] = s.v[i];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) o[16 + i] = s.w[i];
-    }
+    ant_observe(s, g, o);
     float acc = b1;
 #pragma unroll
     for (int i = 0; i < 27; ++i) acc = fmaf(o[i], w1[i], acc);
@@ -1011,37 +787,23 @@ __global__ void __launch_bounds__(64 * ANT_WAVES, 2) ant_rollout_reg_kernel(cons
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    float a2;
-    if constexpr (KM == 0) {
-      float c4[4] = {b2, 0.f, 0.f, 0.f};
+    ant_f4 m[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    float c2[2] = {b2, 0.f};
 #pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const float4 a = reinterpret_cast<const float4*>(a1s)[i];
-        c4[0] = fmaf(a.x, w2[4 * i], c4[0]);
-        c4[1] = fmaf(a.y, w2[4 * i + 1], c4[1]);
-        c4[2] = fmaf(a.z, w2[4 * i + 2], c4[2]);
-        c4[3] = fmaf(a.w, w2[4 * i + 3], c4[3]);
+    for (int i = 0; i < 16; ++i) {
+      const float4 a = reinterpret_cast<const float4*>(a1s)[i];
+      const float av[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int k = 4 * i + q;
+        if (k < ANT_L2_MFMA)
+          m[q & 1] = __builtin_amdgcn_mfma_f32_4x4x1f32(w2[k], av[q], m[q & 1], 0, 0, 0);
+        else
+          c2[q & 1] = fmaf(av[q], w2[k], c2[q & 1]);
       }
-      a2 = fast_tanh((c4[0] + c4[1]) + (c4[2] + c4[3]));
-    } else {
-      ant_f4 m[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-      float c2[2] = {b2, 0.f};
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const float4 a = reinterpret_cast<const float4*>(a1s)[i];
-        const float av[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int k = 4 * i + q;
-          if (k < KM)
-            m[q & 1] = __builtin_amdgcn_mfma_f32_4x4x1f32(w2[k], av[q], m[q & 1], 0, 0, 0);
-          else
-            c2[q & 1] = fmaf(av[q], w2[k], c2[q & 1]);
-        }
-      }
-      const int r = lane & 3;
-      a2 = fast_tanh((m[0][r] + m[1][r]) + (c2[0] + c2[1]));
     }
+    const int r = lane & 3;
+    const float a2 = fast_tanh((m[0][r] + m[1][r]) + (c2[0] + c2[1]));
     // 8 partial products → transposing butterfly reduction
     float v4[4], v2[2], v1;
 #pragma unroll
@@ -1063,89 +825,30 @@ __global__ void __launch_bounds__(64 * ANT_WAVES, 2) ant_rollout_reg_kernel(cons
     }
     v1 = quad_sum(v1);  // lanes ^1, ^2
     v1 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v1), 0x141, 0xF, 0xF, false));  // row_half_mirror: the other quad
-    float tau[8], csum = 0.f;
+    float act[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      // output k lives in the lanes whose bits (5,4,3) spell k
-      const float a = fminf(fmaxf(fast_tanh(rl(v1, ((k >> 2) & 1) * 32 + ((k >> 1) & 1) * 16 + (k & 1) * 8) + b3[k]), -1.f), 1.f);
-      tau[k] = GEAR * a;
-      csum += a * a;
-    }
-    const float th = sel4(leg, tau[0], tau[2], tau[4], tau[6]), ta = sel4(leg, tau[1], tau[3], tau[5], tau[7]);
-    float x0, x1, z1;
-    if constexpr (PK) {
-      x0 = pb.p.xy.x;
-      const f2 tq = f2{th, ta * pl.sg};
-#pragma unroll 1
-      for (int k = 0; k < SUB; ++k) art_substep_pk(pb, pl, tq);
-      x1 = pb.p.xy.x;
-      z1 = pb.p.z;
-    } else {
-      x0 = s.p[0];
-#pragma unroll 1
-      for (int k = 0; k < SUB; ++k) art_substep(s, g, th, ta);
-      x1 = s.p[0];
-      z1 = s.p[2];
-    }
-    const bool healthy = (z1 >= 0.2f) && (z1 <= 1.0f);
-    if (!healthy) break;
-    total += (x1 - x0) * (1.f / (DT * SUB)) + 1.f - 0.5f * csum;
+    for (int k = 0; k < 8; ++k)  // output k lives in the lanes whose bits (5,4,3) spell k
+      act[k] = fminf(fmaxf(fast_tanh(rl(v1, ((k >> 2) & 1) * 32 + ((k >> 1) & 1) * 16 + (k & 1) * 8) + b3[k]), -1.f), 1.f);
+    if (!ant_control<true>(s, g, leg, act, total)) break;
   }
   if (lane == 0) {
     ret[ind] = total;
     if (steps_out) steps_out[ind] = t;
-    if (trace) {  // diagnostics (EVOXMI_ANT_TRACE): shader cycles and the wave's hardware slot
-      ret[ind] = (float)(__builtin_amdgcn_s_memtime() - t_start);
-      steps_out[ind] = (int)((__builtin_amdgcn_s_getreg((31 << 11) | 4) & 0xFFFFu) | ((__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xFu) << 16));
-    }
   }
 }
 
 }  // namespace
 
-int64_t evx_ant_lds_bytes(int64_t P, int h1, int h2, int waves) { return (P + 32 + h1 + h2 + 8) * 4 * waves; }
+int64_t evx_ant_lds_bytes(int64_t P, int h1, int h2, int waves) { return ant_lds_words(P, h1, h2) * 4 * waves; }
 
 void evx_ant_rollout(const float* W, int64_t P, int N, int h1, int h2, const float* init, int cap, float* ret, int* steps, hipStream_t s) {
   if (h1 <= 64 && h2 <= 64) {
-    static const int trace = [] {
-      const char* e = getenv("EVOXMI_ANT_TRACE");
-      return e ? atoi(e) : 0;
-    }();
-    // EVOXMI_ANT_L2_MFMA: the first KM inputs of layer 2 on the matrix cores, concurrently with the
-    // VALU on the rest (north-star K15: the policy's hidden layer on MFMA).  Default 16 — the split
-    // that is fastest for the isolated layer (907 vs 1100 cycles, profiles/r3_k15_mfma_probe.log);
-    // inside the rollout every setting is within noise (1000-step latency 8.63 ms at 0, 8.70 at 16,
-    // 8.67 at 32; profiles/r3_k15_ant_l2_mfma_ab.txt) because layer 2 is ≈5 % of a control step.
-    // 0 = VALU only.
-    static const int km = [] {
-      const char* e = getenv("EVOXMI_ANT_L2_MFMA");
-      return e ? atoi(e) : 16;
-    }();
-    const dim3 grid((N + ANT_WAVES - 1) / ANT_WAVES), block(64 * ANT_WAVES);
-    // EVOXMI_ANT_PACKED: the packed-f32 sub-step (art_substep_pk); 0 = the scalar one
-    static const int pk = [] {
-      const char* e = getenv("EVOXMI_ANT_PACKED");
-      return e ? atoi(e) : 1;
-    }();
-    if (pk) {
-      if (km >= 16)
-        ant_rollout_reg_kernel<16, true><<<grid, block, 0, s>>>(W, P, N, h1, h2, init, cap, ret, steps, trace);
-      else
-        ant_rollout_reg_kernel<0, true><<<grid, block, 0, s>>>(W, P, N, h1, h2, init, cap, ret, steps, trace);
-    } else if (km >= 32)
-      ant_rollout_reg_kernel<32, false><<<grid, block, 0, s>>>(W, P, N, h1, h2, init, cap, ret, steps, trace);
-    else if (km >= 16)
-      ant_rollout_reg_kernel<16, false><<<grid, block, 0, s>>>(W, P, N, h1, h2, init, cap, ret, steps, trace);
-    else if (km >= 8)
-      ant_rollout_reg_kernel<8, false><<<grid, block, 0, s>>>(W, P, N, h1, h2, init, cap, ret, steps, trace);
-    else
-      ant_rollout_reg_kernel<0, false><<<grid, block, 0, s>>>(W, P, N, h1, h2, init, cap, ret, steps, trace);
+    ant_rollout_reg_kernel<<<(N + ANT_WAVES - 1) / ANT_WAVES, 64 * ANT_WAVES, 0, s>>>(W, P, N, h1, h2, init, cap, ret, steps);
     return;
   }
-  const int64_t per = (P + 32 + h1 + h2 + 8) * 4;
   int waves = 4;
-  while (waves > 1 && per * waves > 160 * 1024) --waves;
-  const int blocks = (N + waves - 1) / waves;
-  (void)hipFuncSetAttribute((const void*)ant_rollout_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(per * waves));
-  ant_rollout_kernel<<<blocks, 64 * waves, per * waves, s>>>(W, P, N, h1, h2, init, cap, ret, steps, waves);
+  while (waves > 1 && evx_ant_lds_bytes(P, h1, h2, waves) > EVX_ANT_LDS_LIMIT) --waves;
+  const int64_t lds = evx_ant_lds_bytes(P, h1, h2, waves);
+  (void)hipFuncSetAttribute((const void*)ant_rollout_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  ant_rollout_kernel<<<(N + waves - 1) / waves, 64 * waves, lds, s>>>(W, P, N, h1, h2, init, cap, ret, steps, waves);
 }

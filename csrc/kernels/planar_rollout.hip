@@ -2,7 +2,9 @@
 // inverted_pendulum, inverted_double_pendulum, reacher and any model of the same combinations) with a
 // per-individual MLP policy.
 //
-// Execution model of ant_rollout_kernel (neuro.hip): one wave64 owns one individual for the whole
+// Execution model of the Ant rollout's LDS-resident kernel (ant_rollout_kernel in neuro.hip, the one of its two
+// kernels that keeps the weights in LDS; the physics there is Ant-specific and packed f32, here it is table-driven
+// and scalar): one wave64 owns one individual for the whole
 // episode, its MLP obs-h1-h2-act (tanh) weights live in LDS with lanes striding over units (the first
 // layer's in registers when it has at most 128 units, see w1_in_registers), waves
 // leave independently (sticky done, the terminating step earns nothing) and there is no block

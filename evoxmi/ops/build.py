@@ -76,8 +76,9 @@ def _run(cmd):
 # did; whether SLP packing helps or hurts that kernel has not been measured
 # mo_geom.hip: its distance loop must stay unfused (bit-identical ties with the CPU
 # oracle); plain "fast" contraction ignores the in-source pragma
-# neuro.hip: the Ant sub-step is scalar f32 arithmetic; SLP packing adds ~400 v_mov per
-# sub-step and pushes the register-resident rollout from 230 VGPRs (2 waves / SIMD) to 364
+# neuro.hip: the Ant sub-step is packed f32 by hand (v_pk_* with op_sel / neg swizzles); SLP packing
+# of what is left scalar lengthens it from 642 to 734 instructions and makes the register-resident
+# rollout spill (250 VGPRs and no scratch → 256 and 244 bytes of scratch per lane)
 # gemm_ks.hip: the bf16x6 split's residual subtractions must stay scalar (v_pk_add_f32 issued
 # beside MFMAs costs ≈13 cycles more than two v_sub_f32)
 # knea_select.hip: its contract is float64 arithmetic in a stated operation order with no FMA, so a
@@ -86,7 +87,7 @@ def _run(cmd):
 # bige_select.hip, tdea_select.hip: the same kind of contract: a host implementation reproduces BiGE's proximity and θ-DEA's
 # penalised distance bit for bit
 # hv_exact.hip: its accuracy contract counts one rounding per float64 operation of the stated formulas, so none may fuse
-# planar_rollout.hip: as neuro.hip, its sub-step is scalar f32 arithmetic; SLP packing adds ~190 v_mov per
+# planar_rollout.hip: its sub-step is scalar f32 arithmetic; SLP packing adds ~190 v_mov per
 # sub-step (835 instructions against 704 without it in the two-chain instantiation)
 FILE_FLAGS = {"eigh_sbr.hip": ["-fno-slp-vectorize"], "mo_geom.hip": ["-ffp-contract=fast-honor-pragmas"],
               "knea_select.hip": ["-ffp-contract=off"], "rvea_select.hip": ["-ffp-contract=off"],

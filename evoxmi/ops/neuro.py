@@ -19,6 +19,17 @@ def ant_rollout(flat_weights: torch.Tensor, h1: int, h2: int, init_state: torch.
                                   init_state.to(device=flat_weights.device, dtype=torch.float32).contiguous(), int(cap))
 
 
+def ant_lds_bytes(h1: int, h2: int, waves: int = 1) -> int:
+    """LDS that ``waves`` waves of the LDS-resident Ant kernel (``h1`` or ``h2`` above 64) need.  The launcher
+    puts up to 4 waves in a workgroup, as many as stay within ``ant_lds_limit()``; the binding refuses a policy
+    whose single wave does not."""
+    return _ext.ops().ant_lds_bytes(int(h1), int(h2), int(waves))
+
+
+def ant_lds_limit() -> int:
+    return _ext.ops().ant_lds_limit()
+
+
 def planar_param_count(obs_dim: int, h1: int, h2: int, act_dim: int) -> int:
     return obs_dim * h1 + h1 + h1 * h2 + h2 + h2 * act_dim + act_dim
 

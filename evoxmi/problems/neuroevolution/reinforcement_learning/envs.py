@@ -20,7 +20,7 @@ that keeps each individual's MLP weights in LDS for the whole episode.
   base-acceleration coupling, closed-form Coriolis / centrifugal terms, a 6×6 Schur-complement
   solve per sub-step; see :class:`Ant`), 5 sub-steps of 10 ms per 50 ms control step; total
   momentum is conserved to rounding with no external forces.  The fused kernel integrates the
-  same model on packed-f32 register pairs (``neuro.hip: art_substep_pk``).
+  same model on packed-f32 register pairs (``neuro.hip: ant_substep``).
   Observation (27) = torso z, orientation quaternion, 8 joint angles, torso linear and
   angular velocity, 8 joint velocities (Brax ``qpos[2:] ++ qvel``).  Reward = forward
   velocity + 1 (healthy) − 0.5‖a‖²; the episode ends when torso z leaves [0.2, 1.0].

@@ -636,6 +636,60 @@ def test_ant_rollout_kernel_matches_torch(cap, hidden):
     assert torch.allclose(out.cpu(), ref, rtol=2e-3, atol=2e-3 * cap)
 
 
+@pytest.fixture(scope="module", params=[64, 96])
+def ant_launches(request):
+    """``ant_rollout`` of the first N of 96 weight rows (built as in the test above) for N = 96, 5, 1, 0 at
+    cap 20, and of all 96 at cap 40: ``(hidden, waves per workgroup, {(N, cap): (ret, steps)})``.  Hidden 64 is
+    the register kernel (4 waves per workgroup), 96 the LDS kernel with as many waves, up to 4, as its LDS
+    sizing allows."""
+    from evoxmi.models import MLPPolicy
+    from evoxmi.ops import neuro
+    from evoxmi.problems.neuroevolution.reinforcement_learning.envs import get_environment
+    from evoxmi.utils import TreeAndVector
+
+    hidden = request.param
+    policy = MLPPolicy([27, hidden, hidden, 8])
+    params = policy.init(rnd.PRNGKey(0))
+    tv = TreeAndVector(params)
+    pop = tv.to_vector(params) + 0.3 * torch.randn(96, tv.to_vector(params).numel(), generator=torch.Generator().manual_seed(20))
+    W = policy.flat(tv.batched_to_tree(pop)).cuda()
+    assert W.shape == (96, neuro.ant_param_count(hidden, hidden))
+    s0 = get_environment("ant").reset(rnd.PRNGKey(5), 1)[0][0].cuda()
+    waves = 4 if hidden <= 64 else max(w for w in (1, 2, 3, 4) if neuro.ant_lds_bytes(hidden, hidden, w) <= neuro.ant_lds_limit())
+    out = {(n, cap): tuple(x.cpu() for x in neuro.ant_rollout(W[:n], hidden, hidden, s0, cap))
+           for n, cap in [(96, 20), (5, 20), (1, 20), (0, 20), (96, 40)]}
+    return hidden, waves, out
+
+
+def test_ant_rollout_partial_workgroups_bitwise(ant_launches):
+    """A workgroup whose last waves have no individual (``ind >= N``) computes the same bits for the waves that
+    do: waves are independent and the kernel is deterministic."""
+    hidden, waves, out = ant_launches
+    assert waves == {64: 4, 96: 3}[hidden]
+    ret, steps = out[96, 20]
+    assert ret.shape == (96,) and steps.shape == (96,) and ret.dtype == torch.float32 and steps.dtype == torch.int32
+    for n in (5, 1):
+        assert n % waves != 0  # the last workgroup is partly filled
+        r, s = out[n, 20]
+        assert torch.equal(r, ret[:n]) and torch.equal(s, steps[:n])
+    r, s = out[0, 20]
+    assert r.shape == (0,) and s.shape == (0,)
+
+
+def test_ant_rollout_steps_contract(ant_launches):
+    """``steps`` is the index of the terminating control step, or cap for an episode that did not end.  The
+    terminating step earns nothing and nothing after it counts (sticky done), so a finished episode has the
+    same return under a larger cap."""
+    _, _, out = ant_launches
+    for (n, cap), (r, s) in out.items():
+        assert bool(((s >= 0) & (s <= cap)).all()) and bool(torch.isfinite(r).all())
+    (r20, s20), (r40, s40) = out[96, 20], out[96, 40]
+    ended = s20 < 20
+    assert bool(ended.any()) and not bool(ended.all())  # both cases occur at this weight scale
+    assert torch.equal(s40[ended], s20[ended]) and torch.equal(r40[ended], r20[ended])
+    assert bool((s40[~ended] >= 20).all())
+
+
 def test_ant_rollout_long_episode_statistics():
     from evoxmi.models import MLPPolicy
     from evoxmi.problems.neuroevolution import Brax
