@@ -506,70 +506,44 @@ void sbr_dev_ctrl_rank(const at::Tensor& part, int64_t nparts, int64_t j, int64_
                         prm.size() > 11 ? (int)prm[11] : -1);
 }
 
-std::vector<at::Tensor> argsort_f32(const at::Tensor& keys, int64_t descending) {
-  // 1-D keys, or (B, n): B independent rows sorted by B workgroups of one launch
+// What the two device argsorts share.  Keys are 1-D, or (B, n): B independent rows sorted in one launch
+// (a 0-d key is one row of one key).  Checks the keys, sets the device guard, allocates the sorted keys
+// ok and the int32 indices oi, and hands them to launch(B, n, ok, oi), which checks the op's own grid
+// limit before it launches; empty keys launch nothing.
+template <class Launch>
+std::vector<at::Tensor> argsort_op(const char* op, const at::Tensor& keys, int max_n, Launch launch) {
   CHECK_DEV(keys); CHECK_F32(keys); CHECK_CONTIG(keys);
-  TORCH_CHECK(keys.dim() <= 2, "argsort_f32: keys must be (n,) or (B, n)");
+  TORCH_CHECK(keys.dim() <= 2, op, ": keys must be (n,) or (B, n)");
   const int64_t B = keys.dim() == 2 ? keys.size(0) : 1;
   const int64_t n = keys.dim() == 0 ? 1 : keys.size(-1);
-  TORCH_CHECK(n <= evx_argsort_max_n(), "argsort_f32: n > ", evx_argsort_max_n());
-  TORCH_CHECK(B <= 65535, "argsort_f32: B > 65535");
+  TORCH_CHECK(n <= max_n, op, ": n > ", max_n);
   c10::DeviceGuard g(keys.device());
   auto ok = at::empty_like(keys);
   auto oi = at::empty(keys.sizes(), keys.options().dtype(at::kInt));
-  if (n > 0 && B > 0)
-    evx_argsort(keys.data_ptr<float>(), (int)n, (int)descending, ok.data_ptr<float>(), oi.data_ptr<int32_t>(), cur_stream(), (int)B);
+  launch(B, n, ok, oi);
   return {ok, oi};
 }
 
-// same contract as argsort_f32, rocPRIM block radix sort in one workgroup per row (sort.hip)
-std::vector<at::Tensor> radix_argsort_f32(const at::Tensor& keys, int64_t descending) {
-  CHECK_DEV(keys); CHECK_F32(keys); CHECK_CONTIG(keys);
-  TORCH_CHECK(keys.dim() <= 2, "radix_argsort_f32: keys must be (n,) or (B, n)");
-  const int64_t B = keys.dim() == 2 ? keys.size(0) : 1;
-  const int64_t n = keys.dim() == 0 ? 1 : keys.size(-1);
-  TORCH_CHECK(n <= evx_argsort_max_n(), "radix_argsort_f32: n > ", evx_argsort_max_n());
-  TORCH_CHECK(B <= 65535, "radix_argsort_f32: B > 65535");
-  c10::DeviceGuard g(keys.device());
-  auto ok = at::empty_like(keys);
-  auto oi = at::empty(keys.sizes(), keys.options().dtype(at::kInt));
-  if (n > 0 && B > 0)
-    evx_radix_argsort(keys.data_ptr<float>(), (int)n, (int)descending, ok.data_ptr<float>(), oi.data_ptr<int32_t>(), cur_stream(), (int)B);
-  return {ok, oi};
-}
-
-// same contract as radix_argsort_f32: rank-by-counting, one launch for n ≤ 16384 (sort.hip)
-std::vector<at::Tensor> merge_argsort_f32(const at::Tensor& keys, int64_t descending) {
-  CHECK_DEV(keys); CHECK_F32(keys); CHECK_CONTIG(keys);
-  TORCH_CHECK(keys.dim() <= 2, "merge_argsort_f32: keys must be (n,) or (B, n)");
-  const int64_t B = keys.dim() == 2 ? keys.size(0) : 1;
-  const int64_t n = keys.dim() == 0 ? 1 : keys.size(-1);
-  TORCH_CHECK(n <= evx_merge_argsort_max_n(), "merge_argsort_f32: n > ", evx_merge_argsort_max_n());
-  TORCH_CHECK(B * ((n + 4095) / 4096) <= 65535, "merge_argsort_f32: B * chunks > 65535");
-  c10::DeviceGuard g(keys.device());
-  auto ok = at::empty_like(keys);
-  auto oi = at::empty(keys.sizes(), keys.options().dtype(at::kInt));
-  auto wk = at::empty(keys.sizes(), keys.options().dtype(at::kInt));
-  auto wi = at::empty(keys.sizes(), keys.options().dtype(at::kInt));
-  if (n > 0 && B > 0)
-    evx_merge_argsort(keys.data_ptr<float>(), (int)n, (int)descending, ok.data_ptr<float>(), oi.data_ptr<int32_t>(),
-                      reinterpret_cast<uint32_t*>(wk.data_ptr<int32_t>()), wi.data_ptr<int32_t>(), cur_stream(), (int)B);
-  return {ok, oi};
-}
-
+// rank-by-counting, one launch for n ≤ 16384 (sort.hip)
 std::vector<at::Tensor> rank_argsort_f32(const at::Tensor& keys, int64_t descending) {
-  CHECK_DEV(keys); CHECK_F32(keys); CHECK_CONTIG(keys);
-  TORCH_CHECK(keys.dim() <= 2, "rank_argsort_f32: keys must be (n,) or (B, n)");
-  const int64_t B = keys.dim() == 2 ? keys.size(0) : 1;
-  const int64_t n = keys.dim() == 0 ? 1 : keys.size(-1);
-  TORCH_CHECK(n <= evx_rank_argsort_max_n(), "rank_argsort_f32: n > ", evx_rank_argsort_max_n());
-  TORCH_CHECK(B <= 65535, "rank_argsort_f32: B > 65535");
-  c10::DeviceGuard g(keys.device());
-  auto ok = at::empty_like(keys);
-  auto oi = at::empty(keys.sizes(), keys.options().dtype(at::kInt));
-  if (n > 0 && B > 0)
-    evx_rank_argsort(keys.data_ptr<float>(), (int)n, (int)descending, ok.data_ptr<float>(), oi.data_ptr<int32_t>(), cur_stream(), (int)B);
-  return {ok, oi};
+  return argsort_op("rank_argsort_f32", keys, evx_rank_argsort_max_n(), [&](int64_t B, int64_t n, at::Tensor& ok, at::Tensor& oi) {
+    TORCH_CHECK(B <= 65535, "rank_argsort_f32: B > 65535");
+    if (n > 0 && B > 0)
+      evx_rank_argsort(keys.data_ptr<float>(), (int)n, (int)descending, ok.data_ptr<float>(), oi.data_ptr<int32_t>(), cur_stream(), (int)B);
+  });
+}
+
+// same contract as rank_argsort_f32 for n ≤ 65536: rank inside 4096-key chunks, then a co-rank merge of
+// the sorted chunks (sort.hip)
+std::vector<at::Tensor> merge_argsort_f32(const at::Tensor& keys, int64_t descending) {
+  return argsort_op("merge_argsort_f32", keys, evx_merge_argsort_max_n(), [&](int64_t B, int64_t n, at::Tensor& ok, at::Tensor& oi) {
+    TORCH_CHECK(B * ((n + 4095) / 4096) <= 65535, "merge_argsort_f32: B * chunks > 65535");
+    auto wk = at::empty(keys.sizes(), keys.options().dtype(at::kInt));
+    auto wi = at::empty(keys.sizes(), keys.options().dtype(at::kInt));
+    if (n > 0 && B > 0)
+      evx_merge_argsort(keys.data_ptr<float>(), (int)n, (int)descending, ok.data_ptr<float>(), oi.data_ptr<int32_t>(),
+                        reinterpret_cast<uint32_t*>(wk.data_ptr<int32_t>()), wi.data_ptr<int32_t>(), cur_stream(), (int)B);
+  });
 }
 
 at::Tensor cec_basic(const at::Tensor& Z, int64_t fid, const c10::optional<at::Tensor>& perm, int64_t start, int64_t L,
@@ -1969,8 +1943,6 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("hv_contrib(Tensor S, Tensor P, Tensor count, Tensor alpha) -> Tensor");
   m.def("philox_fill(Tensor key, int n, int dist, int offset) -> Tensor");
   m.def("philox_window(Tensor key, int rows, int dtot, int col0, int own, int row0, int dist) -> Tensor");
-  m.def("argsort_f32(Tensor keys, int descending) -> Tensor[]");
-  m.def("radix_argsort_f32(Tensor keys, int descending) -> Tensor[]");
   m.def("rank_argsort_f32(Tensor keys, int descending) -> Tensor[]");
   m.def("merge_argsort_f32(Tensor keys, int descending) -> Tensor[]");
   m.def("cec_basic(Tensor Z, int fid, Tensor? perm, int start, int L, Tensor? sub, float scale, Tensor? Y, int ystart, int yperm, float clamp=0.0) -> Tensor");
@@ -2099,8 +2071,6 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("jacobi_sweeps", &jacobi_sweeps);
   m.impl("cec_basic", &cec_basic);
   m.impl("cec_compose", &cec_compose);
-  m.impl("argsort_f32", &argsort_f32);
-  m.impl("radix_argsort_f32", &radix_argsort_f32);
   m.impl("rank_argsort_f32", &rank_argsort_f32);
   m.impl("merge_argsort_f32", &merge_argsort_f32);
   m.impl("gemm_f32", &gemm_f32);

@@ -156,9 +156,6 @@ void evx_sym_pack(const float* S, int64_t lds, int d, float* P, hipStream_t s);
 void evx_sym_unpack(const float* P, int d, float* S, int64_t lds, hipStream_t s);
 void evx_cma_center_rows(const float* pop, int64_t ldp, const int32_t* rows, const float* mean, const float* sigma, const float* w, int K,
                          int d, float* Y, hipStream_t s, int64_t ldy = 0, int aug = 0);
-void evx_radix_argsort(const float* keys, int n, int descending, float* out_keys, int32_t* out_idx, hipStream_t s, int batch);
-int evx_argsort_max_n();
-void evx_argsort(const float* keys, int n, int descending, float* out_keys, int32_t* out_idx, hipStream_t s, int batch = 1);
 void evx_cec_basic(const float* Z, int64_t ld, int N, int fid, const int32_t* perm, int start, int L, const float* sub,
                    float scale, const float* Y, int64_t ldy, int ystart, int yperm, float* out, hipStream_t s, float clamp = 0.f);
 // outer round `round` of a sweep (0: within-block pairing, ≥1: circle-method rounds; the

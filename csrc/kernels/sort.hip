@@ -1,164 +1,18 @@
-// Single-workgroup argsort (K19) for populations up to 16384 — register + LDS bitonic.
+// Stable device argsorts of f32 keys (K19), rows of a (B, n) batch sorted independently in one launch.
 //
-// Keys are f32 fitness values mapped to order-preserving u32 and packed with the
-// 32-bit index into one u64, so a single 64-bit compare orders by (key, index):
-// deterministic and identical to a stable sort (torch semantics: NaN is the largest
-// value).  1024 threads each hold E = NP/1024 consecutive elements in registers:
-//   * compare-exchange stages with stride j < E run entirely in registers (the stage
-//     structure is unrolled at compile time so no register is indexed dynamically);
-//   * stages with j ≥ E exchange whole per-thread runs with partner thread t ^ (j/E)
-//     through LDS: one vectorised write (ds_write_b128), barrier, one vectorised read
-//     of the partner's run, barrier.  Runs are padded to 144 B so the ds_read_b128 lane
-//     groups hit distinct banks.
-// At NP = 16384: 55 LDS stages instead of the 105 of an all-LDS bitonic network.
+// Key order: every key is mapped to an order-preserving u32 (ord_key) and ties are broken by
+// index, so the result equals torch.sort(stable=True): NaN (either sign) is the largest key,
+// −0 = +0, and for a descending sort the ordered key is complemented, which keeps ties in index order.
+//   * rank-by-counting (rank_argsort_kernel, evx_rank_argsort, n ≤ 16384): all n keys in LDS,
+//     each workgroup ranks 64 elements against all of them; one launch, no workspace;
+//   * chunked rank + co-rank merge (evx_merge_argsort, n ≤ 65536): the same kernel ranks inside
+//     4096-key chunks, then corank_merge_lds_kernel (n ≤ 32768, sorted chunks staged in LDS) or
+//     corank_merge_kernel (searches in L2) places every element by binary searches of the other chunks.
+// The two single-workgroup argsorts that these replaced are measured in profiles/NOTES.md (K19 table).
 #include "evoxmi_mo.h"
 #include <float.h>
-#include <rocprim/block/block_radix_sort.hpp>
 
 namespace {
-
-template <int E>
-struct Run {
-  unsigned long long v[E];
-};
-
-// in-register compare-exchange for all strides j < E of phase k (e0 = global index of v[0])
-template <int E>
-__device__ __forceinline__ void reg_stages(Run<E>& R, int k, int e0) {
-#pragma unroll
-  for (int j = E / 2; j > 0; j >>= 1) {
-#pragma unroll
-    for (int r = 0; r < E; ++r) {
-      if ((r & j) == 0) {
-        const int e = e0 + r;
-        const bool up = (e & k) == 0;
-        unsigned long long a = R.v[r], b = R.v[r + j];
-        const bool sw = (a > b) == up;
-        R.v[r] = sw ? b : a;
-        R.v[r + j] = sw ? a : b;
-      }
-    }
-  }
-}
-
-template <int LOGN>
-__global__ void __launch_bounds__(1024) bitonic_argsort_kernel(const float* __restrict__ keys, int n, int descending,
-                                                               float* __restrict__ out_keys, int32_t* __restrict__ out_idx) {
-  // one workgroup per row (batched runs sort their rows in one launch)
-  keys += (int64_t)blockIdx.x * n;
-  out_idx += (int64_t)blockIdx.x * n;
-  if (out_keys) out_keys += (int64_t)blockIdx.x * n;
-  constexpr int NP = 1 << LOGN;
-  constexpr int T = 1024;
-  constexpr int E = NP / T;  // 1..16
-  constexpr int RUN_U64 = E < 2 ? E : E + 2;  // pad runs (144 B for E = 16) to spread banks
-  __shared__ unsigned long long s[T * RUN_U64];
-  const int t = threadIdx.x;
-  const int e0 = t * E;
-  Run<E> R;
-#pragma unroll
-  for (int r = 0; r < E; ++r) {
-    const int i = e0 + r;
-    unsigned long long v = 0xFFFFFFFFFFFFFFFFull;
-    if (i < n) {
-      const float k = keys[i];
-      uint32_t o = (k != k) ? (descending ? 0u : 0xFFFFFFFFu) : evx::ord_bits(descending ? -k : k);
-      v = evx::key64(o, (uint32_t)i);
-    }
-    R.v[r] = v;
-  }
-  // phases k ≤ E: entirely in registers
-#pragma unroll
-  for (int k = 2; k <= E; k <<= 1) {
-#pragma unroll
-    for (int j = k / 2; j > 0; j >>= 1) {
-#pragma unroll
-      for (int r = 0; r < E; ++r) {
-        if ((r & j) == 0) {
-          const bool up = ((e0 + r) & k) == 0;
-          unsigned long long a = R.v[r], b = R.v[r + j];
-          const bool sw = (a > b) == up;
-          R.v[r] = sw ? b : a;
-          R.v[r + j] = sw ? a : b;
-        }
-      }
-    }
-  }
-  for (int k = 2 * E; k <= NP; k <<= 1) {
-    for (int j = k >> 1; j >= E; j >>= 1) {
-      const int pt = t ^ (j / E);
-      unsigned long long* mine = s + t * RUN_U64;
-      const unsigned long long* theirs = s + pt * RUN_U64;
-#pragma unroll
-      for (int r = 0; r < E; ++r) mine[r] = R.v[r];
-      __syncthreads();
-      const bool lower = (t & (j / E)) == 0;
-#pragma unroll
-      for (int r = 0; r < E; ++r) {
-        const int e = e0 + r;
-        const bool up = (e & k) == 0;
-        unsigned long long a = R.v[r], b = theirs[r];
-        // lower element keeps min when ascending, upper keeps max
-        const bool take_min = (lower == up);
-        R.v[r] = take_min ? (a < b ? a : b) : (a > b ? a : b);
-      }
-      __syncthreads();
-    }
-    reg_stages<E>(R, k, e0);
-  }
-#pragma unroll
-  for (int r = 0; r < E; ++r) {
-    const int i = e0 + r;
-    if (i < n) {
-      const int32_t src = (int32_t)(R.v[r] & 0xFFFFFFFFu);
-      if (out_keys) out_keys[i] = keys[src];
-      out_idx[i] = src;
-    }
-  }
-}
-
-// Single-workgroup LDS radix argsort (rocPRIM block radix sort, 1024 threads × IT keys
-// held in registers, 8-bit digits): 4 scatter passes through LDS instead of the bitonic
-// network's 55 LDS stages.  Stable: keys are loaded in blocked order with index payloads,
-// padding (the extreme NaN bit pattern, index ≥ n) sorts behind every real key, so ties
-// break by index as in torch.sort(stable=True).
-template <int IT>
-__global__ void __launch_bounds__(1024) radix_argsort_kernel(const float* __restrict__ keys, int n, int descending,
-                                                             float* __restrict__ out_keys, int32_t* __restrict__ out_idx) {
-  using sort_t = rocprim::block_radix_sort<float, 1024, IT, int32_t>;
-  __shared__ typename sort_t::storage_type storage;
-  const float* kb = keys + (int64_t)blockIdx.x * n;
-  float k[IT];
-  int32_t v[IT];
-  // padding sorts behind every real key, NaNs included (largest / smallest NaN bit patterns)
-  const float pad = __uint_as_float(descending ? 0xffffffffu : 0x7fffffffu);
-  // every NaN (either sign bit) becomes the largest key 0x7fffffff, so NaNs sort last when
-  // ascending (tied with the padding, which follows by index) and first when descending, as
-  // torch.sort does; -0.0 becomes +0.0 (torch treats them as equal keys: index order)
-  const float qnan = __uint_as_float(0x7fffffffu);
-#pragma unroll
-  for (int r = 0; r < IT; ++r) {
-    const int i = threadIdx.x * IT + r;
-    float x = i < n ? kb[i] : pad;
-    if (i < n) x = (x != x) ? qnan : (x == 0.f ? 0.f : x);
-    k[r] = x;
-    v[r] = i;
-  }
-  if (descending)
-    sort_t().sort_desc(k, v, storage);
-  else
-    sort_t().sort(k, v, storage);
-  float* ok = out_keys ? out_keys + (int64_t)blockIdx.x * n : nullptr;
-  int32_t* oi = out_idx + (int64_t)blockIdx.x * n;
-#pragma unroll
-  for (int r = 0; r < IT; ++r) {
-    const int i = threadIdx.x * IT + r;
-    if (i < n) {
-      if (ok) ok[i] = kb[v[r]];  // the original bits (NaN payloads, signed zeros)
-      oi[i] = v[r];
-    }
-  }
-}
 
 // Rank-by-counting argsort (K19 at 10⁴-class n): rank(i) = #{j : k_j < k_i or (k_j = k_i and j < i)}
 // on order-preserving u32 keys, so the result is a stable sort.  All n keys sit in LDS; a
@@ -330,29 +184,6 @@ __global__ void __launch_bounds__(1024) corank_merge_lds_kernel(const float* __r
 }
 
 }  // namespace
-
-void evx_radix_argsort(const float* keys, int n, int descending, float* out_keys, int32_t* out_idx, hipStream_t s, int batch) {
-  if (n <= 2048) radix_argsort_kernel<2><<<batch, 1024, 0, s>>>(keys, n, descending, out_keys, out_idx);
-  else if (n <= 4096) radix_argsort_kernel<4><<<batch, 1024, 0, s>>>(keys, n, descending, out_keys, out_idx);
-  else if (n <= 8192) radix_argsort_kernel<8><<<batch, 1024, 0, s>>>(keys, n, descending, out_keys, out_idx);
-  else if (n <= 10240) radix_argsort_kernel<10><<<batch, 1024, 0, s>>>(keys, n, descending, out_keys, out_idx);
-  else if (n <= 12288) radix_argsort_kernel<12><<<batch, 1024, 0, s>>>(keys, n, descending, out_keys, out_idx);
-  else radix_argsort_kernel<16><<<batch, 1024, 0, s>>>(keys, n, descending, out_keys, out_idx);
-}
-
-int evx_argsort_max_n() { return 16384; }
-
-void evx_argsort(const float* keys, int n, int descending, float* out_keys, int32_t* out_idx, hipStream_t s, int batch) {
-  int logn = 10;
-  while ((1 << logn) < n) ++logn;
-  switch (logn) {
-    case 10: bitonic_argsort_kernel<10><<<batch, 1024, 0, s>>>(keys, n, descending, out_keys, out_idx); break;
-    case 11: bitonic_argsort_kernel<11><<<batch, 1024, 0, s>>>(keys, n, descending, out_keys, out_idx); break;
-    case 12: bitonic_argsort_kernel<12><<<batch, 1024, 0, s>>>(keys, n, descending, out_keys, out_idx); break;
-    case 13: bitonic_argsort_kernel<13><<<batch, 1024, 0, s>>>(keys, n, descending, out_keys, out_idx); break;
-    default: bitonic_argsort_kernel<14><<<batch, 1024, 0, s>>>(keys, n, descending, out_keys, out_idx); break;
-  }
-}
 
 int evx_rank_argsort_max_n() { return 16384; }
 

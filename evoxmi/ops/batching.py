@@ -6,13 +6,15 @@ evoxmi HIP ops below would otherwise hit functorch's per-sample fallback (one la
 per run).  Each rule moves the run axis to the front and calls the op's batched form:
 
 * ``philox_words`` / ``philox_fill``: keys (B, 2) → grid.y = run (``rng.hip``);
-* ``argsort_f32`` / ``radix_argsort_f32`` / ``rank_argsort_f32``: keys (B, n) → one workgroup
-  (row of workgroups, rank kernel) per run (``sort.hip``);
+* ``rank_argsort_f32``: keys (B, n) → grid.y = run, a row of workgroups per run (``sort.hip``).
+  The rule is the public op's batched form; ``evoxmi.ops.sort`` itself sends batched keys to
+  ``torch.sort``;
 * ``de_trial``: P (B, rows, d), idx (B, R, K), per-row vectors (B, R), keys (B, 2) →
   grid.y = run, all indices run-local (``evo_ops.hip``).
 
 Each run's words/trials are bit-identical to the single-run op with that run's key
-(``tests/test_batched_runs.py``).  This mirrors the reference's use of ``jax.vmap`` for
+(``tests/test_batched_runs.py``), each run's sorted keys and indices to the op applied row by row
+(``tests/test_kernels_gpu.py``).  This mirrors the reference's use of ``jax.vmap`` for
 independent copies of a workflow (``run/run_de.py:54-114`` runs 32 seeds per function).
 """
 from __future__ import annotations
@@ -43,26 +45,6 @@ def _philox_fill(info, in_dims, key, n, dist, offset):
     return _ext.ops().philox_fill(_front(key, in_dims[0], info.batch_size), n, dist, offset), 0
 
 
-def _argsort_f32(info, in_dims, keys, descending):
-    if in_dims[0] is None:
-        return tuple(_ext.ops().argsort_f32(keys, descending)), (None, None)
-    k = _front(keys, in_dims[0], info.batch_size)
-    if k.dim() != 2:
-        raise NotImplementedError("argsort_f32 vmap rule: per-run keys must be 1-D")
-    ok, oi = _ext.ops().argsort_f32(k, descending)
-    return (ok, oi), (0, 0)
-
-
-def _radix_argsort_f32(info, in_dims, keys, descending):
-    if in_dims[0] is None:
-        return tuple(_ext.ops().radix_argsort_f32(keys, descending)), (None, None)
-    k = _front(keys, in_dims[0], info.batch_size)
-    if k.dim() != 2:
-        raise NotImplementedError("radix_argsort_f32 vmap rule: per-run keys must be 1-D")
-    ok, oi = _ext.ops().radix_argsort_f32(k, descending)
-    return (ok, oi), (0, 0)
-
-
 def _rank_argsort_f32(info, in_dims, keys, descending):
     if in_dims[0] is None:
         return tuple(_ext.ops().rank_argsort_f32(keys, descending)), (None, None)
@@ -87,7 +69,7 @@ def register():
     global _REGISTERED
     if _REGISTERED or not _ext.load(build_if_missing=False):
         return
-    for name, fn in (("philox_words", _philox_words), ("philox_fill", _philox_fill), ("argsort_f32", _argsort_f32),
-                     ("radix_argsort_f32", _radix_argsort_f32), ("rank_argsort_f32", _rank_argsort_f32), ("de_trial", _de_trial)):
+    for name, fn in (("philox_words", _philox_words), ("philox_fill", _philox_fill), ("rank_argsort_f32", _rank_argsort_f32),
+                     ("de_trial", _de_trial)):
         torch.library.register_vmap(f"evoxmi::{name}", fn)
     _REGISTERED = True

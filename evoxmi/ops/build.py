@@ -137,12 +137,6 @@ def build(verbose: bool = True, jobs: int = None) -> str:
         cmd = ["g++"] + host_flags + ["-c", src, "-o", obj]
         if _stale(src, obj, hdr, cmd):
             tasks.append(cmd)
-    for src in sorted(glob.glob(os.path.join(CSRC, "runtime", "*.cpp"))):
-        obj = os.path.join(BUILD, "rt_" + os.path.basename(src) + ".o")
-        objs.append(obj)
-        cmd = ["g++"] + host_flags + ["-fopenmp", "-c", src, "-o", obj]
-        if _stale(src, obj, hdr, cmd):
-            tasks.append(cmd)
     if verbose and tasks:
         print(f"[evoxmi.build] compiling {len(tasks)} translation unit(s) for {ARCH}", flush=True)
     with ThreadPoolExecutor(jobs) as ex:

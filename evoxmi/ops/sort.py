@@ -1,9 +1,9 @@
 """Sorting primitives (K19).  Device path for n ≤ 16384 (every population size of the
 north-star configs): the rank-by-counting argsort of ``sort.hip`` — all keys in LDS, each
 256-thread workgroup ranks 64 elements against all n keys, one launch, no workspace, and
-n/64 workgroups spread over the CUs (the single-workgroup radix/bitonic kernels cannot:
-round 2 measured them at 43.9 / 119.8 µs for n = 10 000 against the library's 32.5,
-profiles/r2_sort_microbench.log).  From 8192 to 32768 keys the two-pass merge sort takes over:
+n/64 workgroups spread over the CUs (the two single-workgroup kernels it replaced could not
+and were removed: 43.9 / 119.8 µs for n = 10 000 against the library's 32.5, K19 table of
+profiles/NOTES.md).  From 8192 to 32768 keys the two-pass merge sort takes over:
 rank inside 4096-key chunks, then place every element by lockstep binary searches of the other
 sorted chunks staged in LDS (17.4 µs at 16 384, 33 µs at 30 000 against torch.sort's 32.8 / 42.6;
 reference primitives: src/evox/algorithms/so/es_variants/sort_utils.py:5-12,
@@ -21,7 +21,7 @@ MAX_DEVICE_SORT = 32768  # two-pass merge up to here; the library radix sort bey
 
 
 def _batched(x) -> bool:
-    """Inside ``torch.vmap`` (BatchedRuns): the custom ops carry no batching rule there."""
+    """Inside ``torch.vmap`` (BatchedRuns): batched keys go to ``torch.sort``, which batches natively."""
     try:
         return bool(torch._C._functorch.is_batchedtensor(x))
     except AttributeError:  # pragma: no cover - older torch

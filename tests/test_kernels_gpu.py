@@ -89,11 +89,13 @@ def test_argsort(n):
 
 
 @pytest.mark.parametrize("n", [2048, 10000, 16384])
-def test_lds_bitonic_argsort_kernel(n):
-    """The single-workgroup LDS kernel itself (argsort() routes n > 2048 to the library sort)."""
+@pytest.mark.parametrize("kernel", ["rank_argsort_f32", "merge_argsort_f32"])
+def test_rank_and_merge_argsort_bitwise_keys(kernel, n):
+    """The two device ops themselves, whatever argsort() routes where: NaN-free keys with one tie come
+    back bit for bit, in stable index order."""
     x = torch.randn(n)
     x[3] = x[5]
-    k, i = _ext.ops().argsort_f32(x.cuda(), 0)
+    k, i = getattr(_ext.ops(), kernel)(x.cuda(), 0)
     rk, ri = torch.sort(x, stable=True)
     assert torch.equal(i.cpu().long(), ri) and torch.equal(k.cpu(), rk)
 
@@ -1036,8 +1038,8 @@ def test_open_es_gpu_matches_stored_noise_update():
 
 @pytest.mark.parametrize("n", [100, 10000, 20000])
 def test_sort_ops_under_vmap_and_on_scalars(n):
-    """ops.sort under torch.vmap (BatchedRuns: the custom ops have no batching rule, so the
-    batched call must take the torch.sort path) and on 0-d keys."""
+    """ops.sort under torch.vmap (BatchedRuns: the library sends batched keys to torch.sort,
+    whether or not the rank op's vmap rule is registered) and on 0-d keys."""
     from evoxmi.ops import sort
 
     x = torch.randn(3, n, device="cuda")
@@ -1051,7 +1053,7 @@ def test_sort_ops_under_vmap_and_on_scalars(n):
 
 @pytest.mark.parametrize("n", [1, 3, 100, 2048, 5000, 10000, 12000, 16383, 16384, 30001, 65536])
 @pytest.mark.parametrize("descending", [0, 1])
-@pytest.mark.parametrize("kernel", ["radix_argsort_f32", "rank_argsort_f32", "merge_argsort_f32"])
+@pytest.mark.parametrize("kernel", ["rank_argsort_f32", "merge_argsort_f32"])
 def test_device_argsort_matches_stable_torch_sort(n, descending, kernel):
     from evoxmi.ops import _ext
 
@@ -1079,6 +1081,40 @@ def test_device_argsort_matches_stable_torch_sort(n, descending, kernel):
     ok, oi = getattr(_ext.ops(), kernel)(kd, descending)
     rv, ri = torch.sort(k, dim=1, descending=bool(descending), stable=True)
     assert torch.equal(oi.cpu().long(), ri) and torch.allclose(ok.cpu(), rv, equal_nan=True)
+
+
+@pytest.mark.parametrize("kernel,max_n", [("rank_argsort_f32", 16384), ("merge_argsort_f32", 65536)])
+def test_device_argsort_binding_edges(kernel, max_n):
+    """The checks and allocation the two ops share: empty keys give empty (float32, int32) outputs of
+    the keys' shape, a 0-d key is one key, and more than max_n keys or a host tensor raise."""
+    op = getattr(_ext.ops(), kernel)
+    for shape in [(0,), (2, 0)]:
+        ok, oi = op(torch.empty(shape, device="cuda"), 0)
+        assert ok.shape == shape and oi.shape == shape and ok.numel() == 0 and oi.numel() == 0
+        assert ok.dtype == torch.float32 and oi.dtype == torch.int32 and ok.is_cuda and oi.is_cuda
+    ok, oi = op(torch.tensor(2.5, device="cuda"), 0)
+    assert ok.shape == () and oi.shape == () and float(ok) == 2.5 and int(oi) == 0
+    assert len(op(torch.zeros(max_n, device="cuda"), 0)[1]) == max_n  # the limit itself is inside
+    with pytest.raises(RuntimeError, match=kernel):
+        op(torch.zeros(max_n + 1, device="cuda"), 0)
+    with pytest.raises(RuntimeError):
+        op(torch.zeros(8), 0)
+
+
+def test_rank_argsort_vmap_rule():
+    """The batching rule of rank_argsort_f32 (ops/batching.py): one launch for the rows of a vmap, equal to
+    a stable torch.sort and bit-identical to the unbatched op applied row by row."""
+    from evoxmi.ops import batching
+
+    batching.register()
+    g = torch.Generator().manual_seed(3)
+    x = (torch.randint(0, 26, (3, 100), generator=g).float() / 7).cuda()  # many ties
+    vk, vi = torch.vmap(lambda r: torch.ops.evoxmi.rank_argsort_f32(r, 0))(x)
+    rk, ri = torch.sort(x, dim=1, stable=True)
+    assert vi.dtype == torch.int32 and torch.equal(vi.long(), ri) and torch.equal(vk, rk)
+    for b in range(3):
+        k, i = torch.ops.evoxmi.rank_argsort_f32(x[b].contiguous(), 0)
+        assert torch.equal(vk[b], k) and torch.equal(vi[b], i)
 
 
 def test_linear_gp_fit_kernel_matches_torch():
