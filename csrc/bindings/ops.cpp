@@ -887,36 +887,59 @@ at::Tensor weighted_rowsum(const at::Tensor& X, const c10::optional<at::Tensor>&
 
 void gemm_set_config(int64_t cfg) { evx_gemm_set_config((int)cfg); }
 
+// sbx / pm: x (n, d) with keys of 4 words, or B batched runs x (B, n, d) with keys of 4 words per run
+// (one launch, grid.y = run; lb / ub are shared by the runs)
 at::Tensor sbx(const at::Tensor& x, const at::Tensor& keys, double pro_c, double dis_c, int64_t type, int64_t col0, int64_t dtot) {
   CHECK_DEV(x); CHECK_F32(x); CHECK_CONTIG(x); CHECK_DEV(keys);
-  TORCH_CHECK(x.dim() == 2, "x must be (n, d)");
-  TORCH_CHECK(keys.scalar_type() == at::kLong && keys.is_contiguous() && keys.numel() == 4, "keys must be int64[2,2]");
+  TORCH_CHECK(x.dim() == 2 || x.dim() == 3, "x must be (n, d) or (B, n, d)");
+  const int64_t B = x.dim() == 3 ? x.size(0) : 1;
+  TORCH_CHECK(B <= 65535, "sbx: at most 65535 runs");
+  TORCH_CHECK(keys.scalar_type() == at::kLong && keys.is_contiguous() && keys.numel() == 4 * B, "keys must be int64[2,2] (per run)");
   TORCH_CHECK(type == 1 || type == 2, "type must be 1 or 2");
-  const int64_t n = x.size(0), d = x.size(1);
+  const int64_t n = x.size(-2), d = x.size(-1);
   TORCH_CHECK(dtot == 0 || (col0 >= 0 && col0 + d <= dtot), "column block outside the decision axis");
   c10::DeviceGuard g(x.device());
   const int64_t rows = type == 1 ? n : n / 2;
-  auto out = at::empty({rows, d}, x.options());
-  if (rows > 0 && d > 0) evx_sbx(x.data_ptr<float>(), out.data_ptr<float>(), (int)n, (int)d, keys.data_ptr<int64_t>(), (float)pro_c, (float)dis_c, (int)type, cur_stream(), (int)col0, (int)dtot);
+  auto out = x.dim() == 3 ? at::empty({B, rows, d}, x.options()) : at::empty({rows, d}, x.options());
+  if (B > 0 && rows > 0 && d > 0)
+    evx_sbx(x.data_ptr<float>(), out.data_ptr<float>(), (int)n, (int)d, keys.data_ptr<int64_t>(), (float)pro_c, (float)dis_c, (int)type,
+            cur_stream(), (int)col0, (int)dtot, (int)B);
   return out;
 }
 
 at::Tensor pm(const at::Tensor& x, const at::Tensor& lb, const at::Tensor& ub, const at::Tensor& keys, double pro_m, double dis_m, int64_t nm,
               int64_t col0, int64_t dtot) {
   CHECK_DEV(x); CHECK_F32(x); CHECK_CONTIG(x); CHECK_DEV(lb); CHECK_F32(lb); CHECK_CONTIG(lb); CHECK_DEV(ub); CHECK_F32(ub); CHECK_CONTIG(ub);
-  TORCH_CHECK(keys.scalar_type() == at::kLong && keys.is_contiguous() && keys.numel() == 4, "keys must be int64[2,2]");
-  TORCH_CHECK(x.dim() == 2 && lb.numel() == x.size(1) && ub.numel() == x.size(1), "shape mismatch");
-  TORCH_CHECK(dtot == 0 || (col0 >= 0 && col0 + x.size(1) <= dtot), "column block outside the decision axis");
+  TORCH_CHECK(x.dim() == 2 || x.dim() == 3, "x must be (n, d) or (B, n, d)");
+  const int64_t B = x.dim() == 3 ? x.size(0) : 1;
+  TORCH_CHECK(B <= 65535, "pm: at most 65535 runs");
+  CHECK_DEV(keys);
+  TORCH_CHECK(keys.scalar_type() == at::kLong && keys.is_contiguous() && keys.numel() == 4 * B, "keys must be int64[2,2] (per run)");
+  TORCH_CHECK(lb.numel() == x.size(-1) && ub.numel() == x.size(-1), "shape mismatch");
+  TORCH_CHECK(dtot == 0 || (col0 >= 0 && col0 + x.size(-1) <= dtot), "column block outside the decision axis");
   c10::DeviceGuard g(x.device());
   auto out = at::empty_like(x);
   if (x.numel() > 0)
-    evx_pm(x.data_ptr<float>(), out.data_ptr<float>(), (int)x.size(0), (int)x.size(1), (int)nm, lb.data_ptr<float>(), ub.data_ptr<float>(),
-           keys.data_ptr<int64_t>(), (float)pro_m, (float)dis_m, cur_stream(), (int)col0, (int)dtot);
+    evx_pm(x.data_ptr<float>(), out.data_ptr<float>(), (int)x.size(-2), (int)x.size(-1), (int)nm, lb.data_ptr<float>(), ub.data_ptr<float>(),
+           keys.data_ptr<int64_t>(), (float)pro_m, (float)dis_m, cur_stream(), (int)col0, (int)dtot, (int)B);
   return out;
+}
+
+// f (B, n, m): B independent runs, one workgroup per run (nds_batched.hip) → rank (B, n); `limit` holds per run
+static at::Tensor nds_batched(const at::Tensor& f, int64_t limit) {
+  const int64_t B = f.size(0), n = f.size(1), m = f.size(2);
+  TORCH_CHECK(m >= 1 && m <= evx_nds_batched_max_m(), "nds: batched fitness must be (B, n, m) with m <= ", evx_nds_batched_max_m());
+  TORCH_CHECK(n <= evx_nds_batched_max_n(), "nds: batched runs need n <= ", evx_nds_batched_max_n(), " rows per run");
+  c10::DeviceGuard g(f.device());
+  auto rank = at::empty({B, n}, f.options().dtype(at::kInt));
+  if (limit <= 0 || limit > n) limit = n;
+  if (B > 0 && n > 0) evx_nds_batched(f.data_ptr<float>(), (int)B, (int)n, (int)m, (int)limit, rank.data_ptr<int>(), cur_stream());
+  return rank;
 }
 
 at::Tensor nds(const at::Tensor& f, int64_t limit, const c10::optional<at::Tensor>& err) {
   CHECK_DEV(f); CHECK_F32(f); CHECK_CONTIG(f);
+  if (f.dim() == 3) return nds_batched(f, limit);
   TORCH_CHECK(f.dim() == 2 && f.size(1) >= 1 && f.size(1) <= 8, "fitness must be (n, m) with m <= 8");
   const int64_t n = f.size(0), nw = (n + 31) / 32;
   TORCH_CHECK(n <= 65536, "nds: n <= 65536");
@@ -1435,15 +1458,21 @@ std::vector<at::Tensor> cma_eig_out(const at::Tensor& Bp, const at::Tensor& w, i
   return {B, D, BD};
 }
 
+// rank (n,), f (n, m) → keep (N,); or B batched runs, rank (B, n), f (B, n, m) → keep (B, N), one workgroup per run
 at::Tensor nsga_select(const at::Tensor& rank, const at::Tensor& f, int64_t N, int64_t mask_pos) {
   CHECK_DEV(rank); CHECK_CONTIG(rank); CHECK_DEV(f); CHECK_F32(f); CHECK_CONTIG(f);
-  TORCH_CHECK(rank.scalar_type() == at::kInt && f.dim() == 2 && rank.numel() == f.size(0), "nsga_select: rank int32 (n,), f (n, m)");
-  const int64_t n = f.size(0);
+  const bool batched = f.dim() == 3;
+  TORCH_CHECK(rank.scalar_type() == at::kInt && (batched ? rank.dim() == 2 && rank.size(0) == f.size(0) && rank.size(1) == f.size(1)
+                                                         : f.dim() == 2 && rank.numel() == f.size(0)),
+              "nsga_select: rank int32 (n,), f (n, m), or rank (B, n), f (B, n, m)");
+  const int64_t B = batched ? f.size(0) : 1, n = f.size(-2);
   TORCH_CHECK(n >= 1 && n <= 8192, "nsga_select: 1 <= n <= 8192");
   TORCH_CHECK(N >= 1 && N <= n && mask_pos >= N - 1 && mask_pos < n, "nsga_select: need N <= n and N-1 <= mask_pos < n");
   c10::DeviceGuard g(f.device());
-  auto keep = at::empty({N}, f.options().dtype(at::kLong));
-  evx_nsga_select(rank.data_ptr<int>(), f.data_ptr<float>(), (int)n, (int)f.size(1), (int)N, (int)mask_pos, keep.data_ptr<int64_t>(), cur_stream());
+  auto keep = batched ? at::empty({B, N}, f.options().dtype(at::kLong)) : at::empty({N}, f.options().dtype(at::kLong));
+  if (B > 0)
+    evx_nsga_select(rank.data_ptr<int>(), f.data_ptr<float>(), (int)n, (int)f.size(-1), (int)N, (int)mask_pos, keep.data_ptr<int64_t>(),
+                    cur_stream(), (int)B);
   return keep;
 }
 

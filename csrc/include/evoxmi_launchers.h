@@ -186,9 +186,9 @@ void evx_weighted_rowsum(const float* X, int64_t ldx, const int32_t* idx, const 
                          float* partial, int chunks, hipStream_t s);
 void evx_gemm_set_config(int cfg);
 void evx_sbx(const float* x, float* out, int n, int d, const int64_t* keys, float pro_c, float dis_c, int type, hipStream_t s, int col0 = 0,
-             int dtot = 0);
+             int dtot = 0, int batch = 1);
 void evx_pm(const float* x, float* out, int n, int d, int nm, const float* lb, const float* ub, const int64_t* keys, float pro_m,
-            float dis_m, hipStream_t s, int col0 = 0, int dtot = 0);
+            float dis_m, hipStream_t s, int col0 = 0, int dtot = 0, int batch = 1);
 void evx_dtlz(const float* X, float* F, int N, int D, int M, int variant, hipStream_t s);
 void evx_de_trial(const float* P, const int32_t* idx, const float* coef, int K, const int32_t* cur, const int32_t* mode,
                   const float* CR, const int32_t* jr, const int32_t* L, const int64_t* key, const float* lb, const float* ub,
@@ -209,6 +209,11 @@ size_t evx_nds_workspace_words(int n);
 int evx_nds_peel_blocks(int n);
 void evx_nds(const float* f, int n, int m, int limit, uint32_t* DW, int32_t* rank, uint32_t* ws, int32_t* err, int blocks,
              hipStream_t s);
+// nds_batched.hip: the same ranks for B independent runs, f (B, n, m) → rank (B, n), one workgroup per run
+// (n ≤ evx_nds_batched_max_n(), m ≤ evx_nds_batched_max_m()); limit as for evx_nds, applied per run
+int evx_nds_batched_max_n();
+int evx_nds_batched_max_m();
+void evx_nds_batched(const float* f, int B, int n, int m, int limit, int32_t* rank, hipStream_t s);
 
 // moead.hip
 void evx_moead_parents(const int64_t* nb, int N, int T, const int64_t* key, int32_t* p0, int32_t* p1, hipStream_t s, int row0 = 0);
@@ -235,8 +240,8 @@ void evx_cma_cov_pad(const float* C, const float* S, const float* pc, const floa
 void evx_cma_eig_out(const float* Bp, const float* w, int d, int np, float* B, float* D, float* BdivD, hipStream_t s,
                      const float* Balt = nullptr, const int* keep = nullptr);
 
-// nsga_select.hip
-void evx_nsga_select(const int32_t* rank, const float* f, int n, int m, int N, int mask_pos, int64_t* keep, hipStream_t s);
+// nsga_select.hip: batch runs, rank (batch, n), f (batch, n, m) → keep (batch, N), one workgroup per run
+void evx_nsga_select(const int32_t* rank, const float* f, int n, int m, int N, int mask_pos, int64_t* keep, hipStream_t s, int batch = 1);
 // nsga3_select.hip: NSGA-III niche-preserving selection (n ≤ 8192, R ≤ 8192), idx (N,) ascending rows
 void evx_nsga3_niche_select(const int32_t* rank, const int32_t* last_rank, const int64_t* group, const float* group_dist,
                             const int64_t* key, int n, int N, int R, int64_t* idx, hipStream_t s);

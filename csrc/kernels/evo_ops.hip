@@ -17,7 +17,8 @@ __device__ __forceinline__ uint32_t word_at(uint64_t i, uint32_t k0, uint32_t k1
 // block, else one gene per thread.  Column block (decision-axis state sharding): x / out
 // hold columns [col0, col0 + d) of a dtot-dimensional population and every gene word is
 // drawn at its global counter i·dtot + col0 + j, so a block equals those columns of the
-// unsharded offspring.
+// unsharded offspring.  Batched runs: grid.y = run b, with its own x (n, d), out and 4 key words; the row
+// counters are run-local, so run b's offspring equal the single-run launch with run b's keys.
 __device__ __forceinline__ float sbx_beta(uint32_t w, float e) {
   const float mu = evx::u24(w);
   float beta = mu <= 0.5f ? exp2f(e * __log2f(2.f * mu)) : exp2f(-e * __log2f(2.f - 2.f * mu));
@@ -30,6 +31,9 @@ __global__ void __launch_bounds__(256) sbx_kernel(const float* __restrict__ x, f
                                                   const int64_t* __restrict__ keys, float pro_c, float dis_c, int type, int col0,
                                                   int dtot) {
   const int np = n / 2;
+  x += (int64_t)blockIdx.y * n * d;
+  out += (int64_t)blockIdx.y * (type == 1 ? n : np) * d;
+  keys += 4 * blockIdx.y;
   const uint32_t kg0 = (uint32_t)keys[0], kg1 = (uint32_t)keys[1];
   const uint32_t kp0 = (uint32_t)keys[2], kp1 = (uint32_t)keys[3];
   const float e = 1.f / (dis_c + 1.f);
@@ -68,6 +72,9 @@ __global__ void __launch_bounds__(256) pm_kernel(const float* __restrict__ x, fl
                                                  const int64_t* __restrict__ keys, float pro_m, float dis_m, int col0, int dtot) {
   // column block: lb / ub are the block's, site probability and counters use the global column
   const int64_t total = (int64_t)n * d;
+  x += (int64_t)blockIdx.y * total;  // batched runs: grid.y = run, lb / ub shared
+  out += (int64_t)blockIdx.y * total;
+  keys += 4 * blockIdx.y;
   uint32_t ks0 = (uint32_t)keys[0], ks1 = (uint32_t)keys[1];
   uint32_t ku0 = (uint32_t)keys[2], ku1 = (uint32_t)keys[3];
   const float e1 = dis_m + 1.f, inv = 1.f / (dis_m + 1.f);
@@ -175,13 +182,13 @@ __global__ void __launch_bounds__(256) de_trial_kernel(const float* __restrict__
 }  // namespace
 
 void evx_sbx(const float* x, float* out, int n, int d, const int64_t* keys, float pro_c, float dis_c, int type, hipStream_t s, int col0,
-             int dtot) {
-  sbx_kernel<<<grid_for((int64_t)(n / 2) * d), 256, 0, s>>>(x, out, n, d, keys, pro_c, dis_c, type, col0, dtot > 0 ? dtot : d);
+             int dtot, int batch) {
+  sbx_kernel<<<dim3(grid_for((int64_t)(n / 2) * d), batch), 256, 0, s>>>(x, out, n, d, keys, pro_c, dis_c, type, col0, dtot > 0 ? dtot : d);
 }
 
 void evx_pm(const float* x, float* out, int n, int d, int nm, const float* lb, const float* ub, const int64_t* keys, float pro_m,
-            float dis_m, hipStream_t s, int col0, int dtot) {
-  pm_kernel<<<grid_for((int64_t)n * d), 256, 0, s>>>(x, out, n, d, nm, lb, ub, keys, pro_m, dis_m, col0, dtot > 0 ? dtot : d);
+            float dis_m, hipStream_t s, int col0, int dtot, int batch) {
+  pm_kernel<<<dim3(grid_for((int64_t)n * d), batch), 256, 0, s>>>(x, out, n, d, nm, lb, ub, keys, pro_m, dis_m, col0, dtot > 0 ? dtot : d);
 }
 
 void evx_de_trial(const float* P, const int32_t* idx, const float* coef, int K, const int32_t* cur, const int32_t* mode,

@@ -29,18 +29,20 @@
 //      lowers its owned counts by the members of the new front that dominate them.  Each iteration ranks
 //      at least one member, so there are at most c of them;
 //   4. crowding on the cut front and the (−cd, slot) sort: evx::crowd_select.
+// The compaction and the count passes of steps 2 and 3 are evoxmi_peel.h, shared with nds_batched.hip.
 // The objectives are padded with zeros to MT ∈ {4, 16} per row (equal in both rows of a pair, so the
 // padding never changes a comparison), which keeps the pair loop free of a loop over m.
 #include "evoxmi_crowd.h"
 #include "evoxmi_launchers.h"
+#include "evoxmi_peel.h"
 
 namespace {
 
 constexpr int M2M_THREADS = evx::CROWD_THREADS;
 constexpr int M2M_WAVES = M2M_THREADS / 64;
-constexpr int M2M_ITEMS = 8;
+constexpr int M2M_ITEMS = evx::PEEL_ITEMS;
 constexpr int M2M_MAXN = M2M_THREADS * M2M_ITEMS;  // 8192
-constexpr int M2M_TILE = 4096;                     // floats: 1024 candidates at MT = 4, 256 at MT = 16
+constexpr int M2M_TILE = evx::PEEL_TILE;           // floats: 1024 candidates at MT = 4, 256 at MT = 16
 
 struct M2MShared {
   union {
@@ -57,61 +59,12 @@ struct M2MShared {
   float key0, keyl;
 };
 
-// Ordered compaction of up to 8 flags per thread, flag `ch` (bit ch of `flags`) standing for element
-// ch·1024 + t: pre[ch] becomes the number of flagged elements before it, the return value their total.
-__device__ __forceinline__ int compact(uint32_t flags, int nch, int* wcnt, int (&pre)[M2M_ITEMS]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int ch = 0; ch < M2M_ITEMS; ++ch) {
-    pre[ch] = 0;
-    if (ch < nch) {
-      const unsigned long long b = __ballot((flags >> ch) & 1u);
-      pre[ch] = __popcll(b & ((1ull << lane) - 1ull));
-      if (lane == 0) wcnt[ch * M2M_WAVES + wave] = __popcll(b);
-    }
-  }
-  __syncthreads();
-  int tot = 0;
-  for (int j = 0; j < nch * M2M_WAVES; ++j) {
-    const int v = wcnt[j];
-#pragma unroll
-    for (int ch = 0; ch < M2M_ITEMS; ++ch) pre[ch] += j < ch * M2M_WAVES + wave ? v : 0;
-    tot += v;
-  }
-  __syncthreads();  // wcnt is free again
-  return tot;
-}
-
-template <int MT>
-__device__ __forceinline__ void load_row(const float* __restrict__ f, int row, int m, float (&x)[MT]) {
-#pragma unroll
-  for (int o = 0; o < MT; ++o) x[o] = o < m ? f[(int64_t)row * m + o] : 0.f;
-}
-
-// the number of the tile's first `tl` rows that dominate `own`
-template <int MT>
-__device__ __forceinline__ int count_dominators(const float* tile, int tl, const float (&own)[MT]) {
-  int cnt = 0;
-  for (int i = 0; i < tl; ++i) {
-    bool le = true, lt = false;  // the test of evx::dominates (evoxmi_mo.h), written out: with the helper the kernel grows by 24 bytes
-#pragma unroll
-    for (int o = 0; o < MT; ++o) {
-      const float a = tile[i * MT + o];
-      le = le && a <= own[o];
-      lt = lt || a < own[o];
-    }
-    cnt += (le && lt) ? 1 : 0;
-  }
-  return cnt;
-}
-
 template <int MT>
 __global__ void __launch_bounds__(M2M_THREADS) m2m_select_kernel(const float* __restrict__ f, const void* __restrict__ region, int region64,
                                                                   const int64_t* __restrict__ rad, int n, int m, int S,
                                                                   int64_t* __restrict__ part, int32_t* __restrict__ counts,
                                                                   int32_t* __restrict__ worst) {
   __shared__ M2MShared sh;
-  constexpr int TL = M2M_TILE / MT;
   const int t = threadIdx.x, k = blockIdx.x;
   int64_t* out = part + (int64_t)k * S;
   int pre[M2M_ITEMS];
@@ -127,7 +80,7 @@ __global__ void __launch_bounds__(M2M_THREADS) m2m_select_kernel(const float* __
       flags |= (g == (int64_t)k ? 1u : 0u) << ch;
     }
   }
-  const int c = compact(flags, nch, sh.wcnt, pre);
+  const int c = evx::peel_compact<M2M_THREADS>(flags, nch, sh.wcnt, pre);
 #pragma unroll
   for (int ch = 0; ch < M2M_ITEMS; ++ch)
     if ((flags >> ch) & 1u) sh.mem[pre[ch]] = (uint32_t)(ch * M2M_THREADS + t);
@@ -148,26 +101,8 @@ __global__ void __launch_bounds__(M2M_THREADS) m2m_select_kernel(const float* __
     cnt[it] = 0;
     alive |= (it * M2M_THREADS + t < c ? 1u : 0u) << it;
   }
-  for (int tb = 0; tb < c; tb += TL) {
-    const int tl = min(TL, c - tb);
-    if (tb) __syncthreads();  // the tile is read no more
-    for (int e = t; e < M2M_TILE; e += M2M_THREADS) {
-      const int i = e / MT, o = e % MT;
-      sh.u.tile[e] = (i < tl && o < m) ? f[(int64_t)sh.mem[tb + i] * m + o] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int it = 0; it < nit; ++it) {
-      int d = 0;
-      if ((alive >> it) & 1u) {
-        float own[MT];
-        load_row<MT>(f, (int)sh.mem[it * M2M_THREADS + t], m, own);
-        d = count_dominators<MT>(sh.u.tile, tl, own);
-      }
-#pragma unroll
-      for (int j = 0; j < M2M_ITEMS; ++j) cnt[j] += j == it ? d : 0;  // cnt stays in registers
-    }
-  }
+  const auto member = [&](int slot) { return (int)sh.mem[slot]; };
+  evx::peel_count_pass<MT, M2M_THREADS, false>(f, m, sh.u.tile, c, nit, alive, cnt, false, member, member);
 
   // 3. peel
   int off = 0, rank = 0, F = 0;
@@ -176,7 +111,7 @@ __global__ void __launch_bounds__(M2M_THREADS) m2m_select_kernel(const float* __
     flags = 0;
 #pragma unroll
     for (int it = 0; it < M2M_ITEMS; ++it) flags |= (((alive >> it) & 1u) && (cnt[it] <= 0 || force) ? 1u : 0u) << it;
-    const int tot = compact(flags, nit, sh.wcnt, pre);  // its barriers also end the reads of tile and srow
+    const int tot = evx::peel_compact<M2M_THREADS>(flags, nit, sh.wcnt, pre);  // its barriers also end the reads of tile and srow
     if (tot == 0) {  // cannot happen (dominance is a strict partial order); keeps the loop finite regardless
       force = true;
       continue;
@@ -197,26 +132,8 @@ __global__ void __launch_bounds__(M2M_THREADS) m2m_select_kernel(const float* __
       }
     }
     alive &= ~flags;
-    for (int tb = 0; tb < tot; tb += TL) {
-      const int tl = min(TL, tot - tb);
-      __syncthreads();  // srow is written, the tile is read no more
-      for (int e = t; e < M2M_TILE; e += M2M_THREADS) {
-        const int i = e / MT, o = e % MT;
-        sh.u.tile[e] = (i < tl && o < m) ? f[(int64_t)sh.mem[sh.srow[tb + i]] * m + o] : 0.f;
-      }
-      __syncthreads();
-#pragma unroll 1
-      for (int it = 0; it < nit; ++it) {
-        int d = 0;
-        if ((alive >> it) & 1u) {
-          float own[MT];
-          load_row<MT>(f, (int)sh.mem[it * M2M_THREADS + t], m, own);
-          d = count_dominators<MT>(sh.u.tile, tl, own);
-        }
-#pragma unroll
-        for (int j = 0; j < M2M_ITEMS; ++j) cnt[j] -= j == it ? d : 0;
-      }
-    }
+    // srow is written and the tile is read no more after the pass's first barrier
+    evx::peel_count_pass<MT, M2M_THREADS, true>(f, m, sh.u.tile, tot, nit, alive, cnt, true, [&](int i) { return (int)sh.mem[sh.srow[i]]; }, member);
     off += tot;
     ++rank;
   }

@@ -28,6 +28,8 @@
 // agrees with torch.sort (NaN last, ±0 equal, stable ties).
 // It replaces ~60 small library launches (sorts, gathers, scatters, lexsort) per
 // generation with one.
+// Batched runs: workgroup b selects among run b's rows, rank (B, n) and f (B, n, m) → keep (B, N).  The
+// workgroups share nothing, so row b is the single-run result on run b.
 #include "evoxmi_crowd.h"
 
 namespace {
@@ -59,6 +61,9 @@ __global__ void __launch_bounds__(SEL_THREADS) nsga_select_kernel(const int32_t*
   __shared__ SelShared sh;
   const int t = threadIdx.x;
   const int base = t * SEL_ITEMS;
+  rank += (int64_t)blockIdx.x * n;
+  f += (int64_t)blockIdx.x * n * m;
+  keep += (int64_t)blockIdx.x * N;
 
   // 1. stable sort of rows by rank.  Unranked rows (rank n, past the early stop) map to
   // max ranked + 1, so the radix sort only walks the bits the ranks actually use.
@@ -110,6 +115,6 @@ __global__ void __launch_bounds__(SEL_THREADS) nsga_select_kernel(const int32_t*
 
 }  // namespace
 
-void evx_nsga_select(const int32_t* rank, const float* f, int n, int m, int N, int mask_pos, int64_t* keep, hipStream_t s) {
-  nsga_select_kernel<<<1, SEL_THREADS, 0, s>>>(rank, f, n, m, N, mask_pos, keep);
+void evx_nsga_select(const int32_t* rank, const float* f, int n, int m, int N, int mask_pos, int64_t* keep, hipStream_t s, int batch) {
+  nsga_select_kernel<<<batch, SEL_THREADS, 0, s>>>(rank, f, n, m, N, mask_pos, keep);
 }

@@ -13,6 +13,16 @@ algorithm alone from that key (``tests/test_batched_runs.py``).  The HIP ops use
 DE zoo (Philox streams, the fused trial kernel, sorts) carry vmap rules that fold the run
 axis into their launch (``evoxmi/ops/batching.py``), so a batched generation costs the
 same number of launches as a single run.
+
+NSGA-II and GDE3 batch the same way (``tests/test_batched_mo.py``, ``tests/test_batched_mo_gpu.py``):
+on a HIP device their non-dominated sort, NSGA-II selection, SBX and polynomial mutation have
+batched forms with one workgroup (or one grid row) per run (``nds_batched.hip``, ``nsga_select.hip``,
+``evo_ops.hip``), for merged populations of at most 8192 rows and 8 objectives per run; above those
+caps the batched step raises ``NotImplementedError`` instead of falling back to one launch per run.
+On the CPU their environmental selection, which has data-dependent control flow, runs run by run
+inside one op (``evoxmi.ops.nds.nsga2_survivors_torch``).  The other multi-objective algorithms are not
+covered: their selections read the host or loop on data, and ``BatchedRuns`` over them still raises
+from ``vmap`` (data-dependent control flow, ``.item()``).
 """
 from __future__ import annotations
 

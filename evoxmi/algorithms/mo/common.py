@@ -8,7 +8,6 @@ import torch
 from ...core import Algorithm, State
 from ...operators import crossover, mutation
 from ...parallel.dim_sharded import ColumnSeparable
-from ...operators.selection.non_dominate import crowding_distance, lexsort, non_dominated_sort
 from ...ops import random as rnd
 
 
@@ -69,14 +68,11 @@ class MOAlgorithm(ColumnVariation, Algorithm):
 
 def nsga2_select(fitness, n):
     """Indices of the n survivors by (rank, −crowding) (reference ``eagmoead.py:22-30``)."""
-    if fitness.is_cuda and fitness.shape[0] <= 8192:
-        from ...ops import nds
+    from ...ops import nds
 
+    if fitness.is_cuda and fitness.shape[0] <= 8192:
         return nds.nsga2_survivors(fitness, n, n - 1, until=n)
-    rank = non_dominated_sort(fitness, until=n)
-    worst = torch.sort(rank).values[n - 1]  # 0-d view: no host sync (capturable)
-    cd = crowding_distance(fitness, rank == worst)
-    return lexsort([-cd, rank.to(cd.dtype)])[:n]
+    return nds.nsga2_survivors_torch(fitness, n, n - 1, until=n)  # under vmap: run by run
 
 
 def weights_and_neighbours(w, T):

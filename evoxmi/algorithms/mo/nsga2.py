@@ -13,7 +13,6 @@ import torch
 from ...core import Algorithm, State
 from ...operators import crossover, mutation, selection
 from .common import ColumnVariation
-from ...operators.selection.non_dominate import crowding_distance, lexsort, non_dominated_sort
 from ...ops import random as rnd
 
 
@@ -58,10 +57,8 @@ class NSGA2(ColumnVariation, Algorithm):
 
             keep = nds.nsga2_survivors(merged_fit, self.pop_size, self.pop_size, until=self.pop_size + 1)
             return state.update(population=merged_pop[keep], fitness=merged_fit[keep])
-        rank = non_dominated_sort(merged_fit, until=self.pop_size + 1)
-        # the (pop_size)-th smallest rank, read as a 0-d view (no host sync: graph-capturable)
-        worst = torch.sort(rank).values[self.pop_size]
-        mask = rank == worst
-        cd = crowding_distance(merged_fit, mask)
-        keep = lexsort([-cd, rank.to(cd.dtype)])[: self.pop_size]
+        # the torch path (rank, crowding distance on the cut front, lexsort); under vmap it runs run by run
+        from ...ops import nds
+
+        keep = nds.nsga2_survivors_torch(merged_fit, self.pop_size, self.pop_size, until=self.pop_size + 1)
         return state.update(population=merged_pop[keep], fitness=merged_fit[keep])

@@ -50,8 +50,16 @@ def non_dominated_sort(x: torch.Tensor, method: str = "auto", until: int = 0) ->
 
     ``until`` > 0 (GPU path) stops peeling once at least ``until`` rows are ranked;
     the remaining rows get rank ``n``.  Selection that keeps the best ``k`` rows only
-    needs ``until = k`` (or ``k + 1`` to also read the rank just past the cut)."""
+    needs ``until = k`` (or ``k + 1`` to also read the rank just past the cut).
+
+    ``x`` of shape (B, n, m) is B independent runs: ranks (B, n), row b being the call on
+    ``x[b]``.  On a GPU that is one launch with a workgroup per run (``csrc/kernels/nds_batched.hip``,
+    n ≤ 8192 and m ≤ 8 per run); on the CPU the runs are ranked one after another."""
     assert method in ("auto", "scan", "full map-reduce", "host")
+    if x.dim() == 3 and not (x.is_cuda and method in ("auto", "full map-reduce")):
+        if x.shape[0] == 0:
+            return torch.empty(x.shape[:2], dtype=torch.int32, device=x.device)
+        return torch.stack([non_dominated_sort(xb, method, until) for xb in x])
     if x.is_cuda and method in ("auto", "full map-reduce"):
         from ...ops import nds
 

@@ -10,11 +10,17 @@ per run).  Each rule moves the run axis to the front and calls the op's batched 
   The rule is the public op's batched form; ``evoxmi.ops.sort`` itself sends batched keys to
   ``torch.sort``;
 * ``de_trial``: P (B, rows, d), idx (B, R, K), per-row vectors (B, R), keys (B, 2) →
-  grid.y = run, all indices run-local (``evo_ops.hip``).
+  grid.y = run, all indices run-local (``evo_ops.hip``);
+* ``sbx`` / ``pm``: x (B, n, d), keys (B, 2, 2) → grid.y = run, run-local row counters, bounds shared
+  (``evo_ops.hip``);
+* ``nds``: f (B, n, m) → one workgroup per run (``nds_batched.hip``; n ≤ 8192, m ≤ 8 per run);
+* ``nsga_select``: rank (B, n), f (B, n, m) → one workgroup per run (``nsga_select.hip``).
 
 Each run's words/trials are bit-identical to the single-run op with that run's key
 (``tests/test_batched_runs.py``), each run's sorted keys and indices to the op applied row by row
-(``tests/test_kernels_gpu.py``).  This mirrors the reference's use of ``jax.vmap`` for
+(``tests/test_kernels_gpu.py``), each run's ranks, survivors and offspring to the single-run ops
+(``tests/test_batched_mo_gpu.py``).  A per-run shape above a batched kernel's cap raises
+``NotImplementedError``: there is no silent run-by-run fallback.  This mirrors the reference's use of ``jax.vmap`` for
 independent copies of a workflow (``run/run_de.py:54-114`` runs 32 seeds per function).
 """
 from __future__ import annotations
@@ -63,6 +69,56 @@ def _de_trial(info, in_dims, P, idx, coef, cur, mode, CR, jr, L, key, lb, ub, re
     return _ext.ops().de_trial(*args, lb, ub, repair, err, col0, d_total), 0
 
 
+def _sbx(info, in_dims, x, keys, pro_c, dis_c, type, col0=0, dtot=0):
+    if in_dims[0] is None and in_dims[1] is None:
+        return _ext.ops().sbx(x, keys, pro_c, dis_c, type, col0, dtot), None
+    B = info.batch_size
+    xb = _front(x, in_dims[0], B)
+    if xb.dim() != 3:
+        raise NotImplementedError("sbx vmap rule: per-run x must be (n, d)")
+    return _ext.ops().sbx(xb, _front(keys, in_dims[1], B), pro_c, dis_c, type, col0, dtot), 0
+
+
+def _pm(info, in_dims, x, lb, ub, keys, pro_m, dis_m, nm, col0=0, dtot=0):
+    if in_dims[1] is not None or in_dims[2] is not None:
+        raise NotImplementedError("pm vmap rule: bounds must be shared by all runs")
+    if in_dims[0] is None and in_dims[3] is None:
+        return _ext.ops().pm(x, lb, ub, keys, pro_m, dis_m, nm, col0, dtot), None
+    B = info.batch_size
+    xb = _front(x, in_dims[0], B)
+    if xb.dim() != 3:
+        raise NotImplementedError("pm vmap rule: per-run x must be (n, d)")
+    return _ext.ops().pm(xb, lb, ub, _front(keys, in_dims[3], B), pro_m, dis_m, nm, col0, dtot), 0
+
+
+def _nds(info, in_dims, f, limit=0, err=None):
+    from .nds import check_batched_caps
+
+    # trailing arguments left at their schema defaults are not passed on, so in_dims can be shorter than the signature
+    if len(in_dims) > 2 and in_dims[2] is not None:
+        raise NotImplementedError("nds vmap rule: the error word must be shared by all runs")
+    if in_dims[0] is None:
+        return _ext.ops().nds(f, limit, err), None
+    fb = _front(f, in_dims[0], info.batch_size)
+    if fb.dim() != 3:
+        raise NotImplementedError("nds vmap rule: per-run fitness must be (n, m)")
+    check_batched_caps(fb.shape[1], fb.shape[2], "nds vmap rule")
+    return _ext.ops().nds(fb, limit, None), 0  # one workgroup per run: no grid barrier, so no error path
+
+
+def _nsga_select(info, in_dims, rank, f, N, mask_pos):
+    from .nds import check_batched_caps
+
+    if in_dims[0] is None and in_dims[1] is None:
+        return _ext.ops().nsga_select(rank, f, N, mask_pos), None
+    B = info.batch_size
+    fb = _front(f, in_dims[1], B)
+    if fb.dim() != 3:
+        raise NotImplementedError("nsga_select vmap rule: per-run fitness must be (n, m)")
+    check_batched_caps(fb.shape[1], 1, "nsga_select vmap rule")
+    return _ext.ops().nsga_select(_front(rank, in_dims[0], B), fb, N, mask_pos), 0
+
+
 def register():
     """Install the rules (idempotent).  Without the compiled extension there is nothing to
     batch: CPU tensors never reach the HIP ops, and a device op raises on its own."""
@@ -70,6 +126,6 @@ def register():
     if _REGISTERED or not _ext.load(build_if_missing=False):
         return
     for name, fn in (("philox_words", _philox_words), ("philox_fill", _philox_fill), ("rank_argsort_f32", _rank_argsort_f32),
-                     ("de_trial", _de_trial)):
+                     ("de_trial", _de_trial), ("sbx", _sbx), ("pm", _pm), ("nds", _nds), ("nsga_select", _nsga_select)):
         torch.library.register_vmap(f"evoxmi::{name}", fn)
     _REGISTERED = True

@@ -9,18 +9,30 @@ from .. import config
 from . import random as rnd
 
 
+def _run_keys(key, x, what):
+    """``split(key, 2)`` of one key (2,), or of every run's key (B, 2) for x (B, n, d)."""
+    if x.dim() == 3:
+        if key.dim() != 2 or key.shape[0] != x.shape[0]:
+            raise ValueError(f"{what}: x (B, n, d) needs keys (B, 2), one per run")
+        return torch.stack([rnd.split(k, 2) for k in key]).contiguous()
+    return rnd.split(key, 2).contiguous()
+
+
 def sbx(key, x, pro_c, dis_c, type, cols=None):
-    """``cols = (col0, d_total)``: x is that column block of a d_total-dim population."""
-    keys = rnd.split(key, 2).contiguous()
+    """``cols = (col0, d_total)``: x is that column block of a d_total-dim population.
+    x (B, n, d) with keys (B, 2) is B runs in one launch, run b equal to the call on ``x[b]``, ``key[b]``."""
+    keys = _run_keys(key, x, "sbx")
     c0, dt = cols if cols is not None else (0, 0)
     return _ext.ops().sbx(x.contiguous(), keys, float(pro_c), float(dis_c), int(type), int(c0), int(dt))
 
 
 def polynomial(key, x, lb, ub, pro_m, dis_m, cols=None):
-    keys = rnd.split(key, 2).contiguous()
+    """x (B, n, d) with keys (B, 2) is B runs in one launch (``lb`` / ``ub`` shared), run b equal to the call on ``x[b]``, ``key[b]``."""
+    keys = _run_keys(key, x, "polynomial")
     c0, dt = cols if cols is not None else (0, 0)
-    nm = x.shape[0] if x.shape[0] == 1 else (x.shape[0] // 2) * 2
-    d = x.shape[1]
+    n = x.shape[-2]
+    nm = n if n == 1 else (n // 2) * 2
+    d = x.shape[-1]
     lb = lb.to(device=x.device, dtype=torch.float32).expand(d).contiguous()
     ub = ub.to(device=x.device, dtype=torch.float32).expand(d).contiguous()
     return _ext.ops().pm(x.contiguous(), lb, ub, keys, float(pro_m), float(dis_m), int(nm), int(c0), int(dt))

@@ -7,9 +7,38 @@ from . import _ext
 from .. import config
 
 
+BATCHED_NDS_CAP = 8192  # nds_batched.hip: one workgroup per run, n ≤ 8192 rows
+NDS_MAX_M = 8  # the nds op's objective cap, single-run and batched
+
+
+def _in_vmap(t: torch.Tensor) -> bool:
+    return torch._C._functorch.is_batchedtensor(t)
+
+
+def check_batched_caps(n: int, m: int, what: str = "non_dominated_sort") -> None:
+    """The per-run caps of the batched device sort and selection; above them there is no batched
+    kernel, and a run-by-run fallback would hide that."""
+    if n > BATCHED_NDS_CAP or m > NDS_MAX_M:
+        raise NotImplementedError(f"{what}: batched runs need n <= {BATCHED_NDS_CAP} rows and m <= {NDS_MAX_M} objectives per run, "
+                                  f"got n = {n}, m = {m}")
+
+
 def non_dominated_sort(f: torch.Tensor, until: int = 0) -> torch.Tensor:
     """Pareto ranks; with ``until`` > 0 fronts are peeled only until ≥ ``until`` rows are
-    ranked and the remaining rows get rank ``n`` (larger than every real rank)."""
+    ranked and the remaining rows get rank ``n`` (larger than every real rank).
+
+    ``f`` of shape (B, n, m) is B independent runs: ranks (B, n), row b being the 2-D call on
+    ``f[b]`` (the stop is per run).  On a HIP device that is one launch of ``nds_batched.hip``,
+    one workgroup per run (n ≤ 8192, m ≤ 8 per run); on the CPU the runs are ranked one by one."""
+    if f.dim() == 3:
+        if not f.is_cuda:
+            from ..operators.selection.non_dominate import non_dominated_sort as nds_torch
+
+            return nds_torch(f, until=until)
+        check_batched_caps(f.shape[1], f.shape[2])
+        return _ext.ops().nds(f.to(torch.float32).contiguous(), int(until), None)
+    if f.is_cuda and _in_vmap(f):  # a run of a batch: the rule of ops/batching.py, which has no form above the caps
+        check_batched_caps(f.shape[0], f.shape[1])
     f = f.to(torch.float32).contiguous()
     if f.shape[0] <= 65536 and f.shape[1] <= 8:
         try:
@@ -18,7 +47,8 @@ def non_dominated_sort(f: torch.Tensor, until: int = 0) -> torch.Tensor:
             if "co-resident" not in str(e):
                 raise
         else:
-            if config.get("debug") and not torch.cuda.is_current_stream_capturing():
+            # the host check reads the error word: not under capture, and not under vmap (the batched kernel has no error path)
+            if config.get("debug") and not torch.cuda.is_current_stream_capturing() and not _in_vmap(rank):
                 _ext.check_kernel_errors()
             return rank
     from ..operators.selection.non_dominate import _peel
@@ -55,10 +85,67 @@ def nsga2_survivors(f: torch.Tensor, N: int, mask_pos: int, until: int = 0) -> t
     Identical to the torch path (``crowding_distance`` + lexsort) for finite objectives.  The
     kernel computes the crowding distance on the cut front alone; the torch path sorts all
     rows with the masked-out ones keyed ``+inf``, so the two differ when a cut-front row
-    holds ``+inf`` (or NaN) while other rows are masked out."""
+    holds ``+inf`` (or NaN) while other rows are masked out.
+
+    ``f`` of shape (B, n, m) is B independent runs: survivors (B, N), row b being the 2-D call
+    on ``f[b]``; two launches for all runs, one workgroup per run in each."""
     f = f.to(torch.float32).contiguous()
+    if f.dim() == 3:
+        check_batched_caps(f.shape[1], f.shape[2], "nsga2_survivors")
     rank = non_dominated_sort(f, until)
     return _ext.ops().nsga_select(rank, f, int(N), int(mask_pos))
+
+
+def _survivors_torch(f: torch.Tensor, N: int, mask_pos: int, until: int) -> torch.Tensor:
+    """The torch path of ``nsga2_survivors`` for one run: the CPU oracle, and the device path above
+    the kernels' caps.  ``worst`` is read as a 0-d view (no host sync: capturable on a device)."""
+    from ..operators.selection.non_dominate import crowding_distance as cd_any, lexsort, non_dominated_sort as nds_any
+
+    rank = nds_any(f, until=until)
+    worst = torch.sort(rank).values[mask_pos]
+    cd = cd_any(f, rank == worst)
+    return lexsort([-cd, rank.to(cd.dtype)])[:N]
+
+
+@torch.library.custom_op("evoxmi_py::nsga2_survivors_runs", mutates_args=())
+def _survivors_runs(f: torch.Tensor, N: int, mask_pos: int, until: int) -> torch.Tensor:
+    """``_survivors_torch`` run by run on f (B, n, m) → (B, N): the torch path has data-dependent
+    control flow on the CPU (the peel loop, the size of the cut front), so ``vmap`` cannot trace
+    through it; this op is what a vmapped call reaches."""
+    return torch.stack([_survivors_torch(fb, N, mask_pos, until) for fb in f])
+
+
+@_survivors_runs.register_fake
+def _(f, N, mask_pos, until):
+    return f.new_empty((f.shape[0], N), dtype=torch.int64)
+
+
+@torch.library.custom_op("evoxmi_py::nsga2_survivors_run", mutates_args=())
+def _survivors_run(f: torch.Tensor, N: int, mask_pos: int, until: int) -> torch.Tensor:
+    return _survivors_torch(f, N, mask_pos, until)
+
+
+@_survivors_run.register_fake
+def _(f, N, mask_pos, until):
+    return f.new_empty((N,), dtype=torch.int64)
+
+
+@torch.library.register_vmap("evoxmi_py::nsga2_survivors_run")
+def _(info, in_dims, f, N, mask_pos, until):
+    # sequential by construction: the oracle of the batched device kernels
+    return _survivors_runs(f.movedim(in_dims[0], 0), N, mask_pos, until), 0
+
+
+def nsga2_survivors_torch(f: torch.Tensor, N: int, mask_pos: int, until: int = 0) -> torch.Tensor:
+    """``nsga2_survivors`` through the torch path (``crowding_distance`` + lexsort): the CPU
+    implementation.  (B, n, m) input, or a call under ``vmap``, applies it run by run."""
+    if f.dim() == 3:
+        return _survivors_runs(f, int(N), int(mask_pos), int(until))
+    if _in_vmap(f):
+        if f.is_cuda:  # above the kernels' caps there is no batched device form
+            check_batched_caps(f.shape[0], f.shape[1], "nsga2_survivors")
+        return _survivors_run(f, int(N), int(mask_pos), int(until))
+    return _survivors_torch(f, N, mask_pos, until)
 
 
 NICHE_SELECT_CAP = 8192  # nsga3_select.hip: one workgroup, n ≤ 8192 rows and R ≤ 8192 niches

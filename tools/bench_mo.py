@@ -15,8 +15,16 @@
   lmocso : LMOCSO pop=4096 on DTLZ2 (m=3, d=500)           — 1×MI355X
   bige  : BiGE pop=4096 on DTLZ2 (m=3, d=500)              — 1×MI355X (two bi-goal estimates per generation)
   tdea  : θ-DEA pop=4096 on DTLZ2 (m=3, d=500)             — 1×MI355X (the pop becomes the count of its reference directions)
+  gde3  : GDE3 pop=4096 on DTLZ2 (m=3, d=500)              — 1×MI355X
   moead : MOEA/D pop=16384 on LSMOP1 (m=3, d=10000), Tchebycheff aggregation
 
+  --runs R (nsga2, gde3): R independent seeds, the protocol of a multi-objective comparison (20–30 runs at
+  pop 100–200).  Without --batched the R seeds run one after another, each its own workflow (and hipGraph);
+  with --batched they are one BatchedRuns workflow, every launch of a generation advancing all R runs.
+  Both modes start run r from split(fold_in(key, 1), R)[r], so they compute the same runs; ms_per_gen is the
+  time of one generation of all R runs, and after the timed region every run's IGD is printed.
+
+python tools/bench_mo.py --algo nsga2|gde3 [--pop 100 --dim 12] --runs 32 [--batched]
 python tools/bench_mo.py --algo nsga2|nsga3|sra|ibea|spea2|bceibea|knea|m2m|rvea|rveaa|lmocso|bige|tdea|moead [--gens 20] [--warmup 3] [--no-graph]
 torchrun --nproc-per-node 8 --master-addr 127.0.0.1 tools/bench_mo.py --algo moead
 
@@ -41,14 +49,14 @@ import torch  # noqa: E402
 
 
 def build(args, dev):
-    from evoxmi.algorithms import BCEIBEA, IBEA, LMOCSO, MOEAD, MOEADM2M, NSGA2, NSGA3, RVEA, SPEA2, SRA, TDEA, BiGE, KnEA, RVEAa
+    from evoxmi.algorithms import GDE3, BCEIBEA, IBEA, LMOCSO, MOEAD, MOEADM2M, NSGA2, NSGA3, RVEA, SPEA2, SRA, TDEA, BiGE, KnEA, RVEAa
     from evoxmi.problems.numerical import DTLZ2, LSMOP1
 
     m = 3
-    if args.algo in ("nsga2", "nsga3", "sra", "ibea", "spea2", "bceibea", "knea", "m2m", "rvea", "rveaa", "lmocso", "bige", "tdea"):
+    if args.algo in ("nsga2", "gde3", "nsga3", "sra", "ibea", "spea2", "bceibea", "knea", "m2m", "rvea", "rveaa", "lmocso", "bige", "tdea"):
         d = args.dim or 500
         lb, ub = torch.zeros(d, device=dev), torch.ones(d, device=dev)
-        algos = {"nsga2": NSGA2, "nsga3": NSGA3, "sra": SRA, "ibea": IBEA, "spea2": SPEA2, "bceibea": BCEIBEA, "knea": KnEA,
+        algos = {"nsga2": NSGA2, "gde3": GDE3, "nsga3": NSGA3, "sra": SRA, "ibea": IBEA, "spea2": SPEA2, "bceibea": BCEIBEA, "knea": KnEA,
                  "m2m": MOEADM2M, "rvea": RVEA, "rveaa": RVEAa, "bige": BiGE, "tdea": TDEA}
         if args.algo == "lmocso":  # its constructor takes n_objs first
             return LMOCSO(m, lb, ub, args.pop or 4096), DTLZ2(d=d, m=m)
@@ -59,12 +67,61 @@ def build(args, dev):
     return MOEAD(lb, ub, m, args.pop or 16384, func_name="tchebycheff"), LSMOP1(d=d, m=m)
 
 
+def _with_algorithm_key(state, algo, key):
+    """Re-initialise the algorithm's sub-state from ``key`` (keeping its node id)."""
+    st, _ = algo._recursive_init(key, algo._node_id, algo._module_name, False)
+    return state.update_child("algorithm", st)
+
+
+def run_seeds(args, dev):
+    """--runs R: R seeds of one algorithm, sequential or as one BatchedRuns workflow; one JSON line."""
+    from evoxmi import random as rnd
+    from evoxmi.algorithms.containers.batched import BatchedRuns
+    from evoxmi.metrics.igd import igd
+    from evoxmi.workflows import StdWorkflow
+
+    R, graph = args.runs, not (args.no_graph or args.cpu)
+    key = rnd.PRNGKey(7, device=dev)
+    akey = rnd.fold_in(key, 1)
+    sync = torch.cuda.synchronize if dev.type == "cuda" else (lambda: None)
+    if args.batched:
+        base, prob = build(args, dev)
+        algo = BatchedRuns(base, R)
+        wf = StdWorkflow(algo, prob, graph=graph)
+        jobs = [(wf, _with_algorithm_key(wf.init(key), algo, akey))]  # BatchedRuns starts run r from split(akey, R)[r]
+    else:
+        jobs = []
+        for k in rnd.split(akey, R):
+            base, prob = build(args, dev)
+            wf = StdWorkflow(base, prob, graph=graph)
+            jobs.append((wf, _with_algorithm_key(wf.init(key), base, k)))
+    for _ in range(1 + args.warmup):
+        jobs = [(wf, wf.step(st)) for wf, st in jobs]
+    sync()
+    t = time.perf_counter()
+    for _ in range(args.gens):
+        jobs = [(wf, wf.step(st)) for wf, st in jobs]
+    sync()
+    dt = (time.perf_counter() - t) / args.gens
+    if args.batched:
+        fits = list(jobs[0][1].get_child_state("algorithm").runs.fitness)
+    else:
+        fits = [st.get_child_state("algorithm").fitness for _, st in jobs]
+    pf = prob.pf().to(dev)
+    igds = [round(float(igd(f, pf)), 6) for f in fits]
+    out = {"config": args.algo, "pop": base.pop_size, "dim": base.dim, "n_objs": 3, "graph": graph, "runs": R, "batched": bool(args.batched),
+           "gens": args.gens, "ms_per_gen": round(dt * 1e3, 3), "ms_per_gen_per_run": round(dt * 1e3 / R, 4),
+           "run_gens_per_sec": round(R / dt, 1), "evals_per_sec": round(R * base.pop_size / dt, 1),
+           "fitness_finite": all(bool(torch.isfinite(f).all()) for f in fits), "igd": igds}
+    print(json.dumps(out), flush=True)
+
+
 def main():
     from evoxmi import random as rnd
     from evoxmi.workflows import StdWorkflow
 
     ap = argparse.ArgumentParser()
-    ap.add_argument("--algo", choices=["nsga2", "nsga3", "sra", "ibea", "spea2", "bceibea", "knea", "m2m", "rvea", "rveaa", "lmocso", "bige", "tdea", "moead"], default="nsga2")
+    ap.add_argument("--algo", choices=["nsga2", "gde3", "nsga3", "sra", "ibea", "spea2", "bceibea", "knea", "m2m", "rvea", "rveaa", "lmocso", "bige", "tdea", "moead"], default="nsga2")
     ap.add_argument("--gpus", type=int, default=1, help="ranks (one per GPU); spawned here unless torchrun started them")
     ap.add_argument("--pop", type=int, default=0)
     ap.add_argument("--dim", type=int, default=0)
@@ -72,6 +129,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--cpu", action="store_true")
+    ap.add_argument("--runs", type=int, default=0, help="nsga2 / gde3: this many independent seeds (one GPU)")
+    ap.add_argument("--batched", action="store_true", help="with --runs: all seeds as one BatchedRuns workflow")
     ap.add_argument("--force-dist", action="store_true", help="sharded protocol even on one rank")
     ap.add_argument("--simulate-rank", type=int, default=None,  # -1 (MOEA/D): the rank with the largest halo
                     help="time rank R's share of a --world N sharded step on this one GPU (collectives → same-size local ops)")
@@ -79,6 +138,10 @@ def main():
     ap.add_argument("--shard", choices=["auto", "owner", "replica"], default="auto", help="MOEA/D sharded mode")
     ap.add_argument("--link-gbps", type=float, default=None, help="--simulate-rank wire model: GB/s per xGMI link and direction")
     args = ap.parse_args()
+    if args.runs or args.batched:
+        if args.algo not in ("nsga2", "gde3") or args.runs < 1 or args.gpus != 1 or args.simulate_rank is not None or args.force_dist:
+            ap.error("--runs R [--batched] needs R >= 1, --algo nsga2 or gde3, and one rank")
+        return run_seeds(args, torch.device("cpu" if args.cpu else "cuda"))
     import torch.distributed as dist
     from evoxmi.parallel import init_distributed
     from evoxmi.parallel.launch import LaunchError, ensure_ranks
