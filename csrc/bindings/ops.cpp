@@ -1721,15 +1721,33 @@ std::vector<at::Tensor> sra_indicators(const at::Tensor& obj) {
   return {I1, I2};
 }
 
+// ibea_select.hip and spea2_select.hip: obj (n, m) is one population, (B, n, m) B independent runs in one launch; the per-row operands
+// are then (B, n) and every output gains the leading B
+struct RunShape {
+  int64_t B, n, m;
+  bool batched;
+  std::vector<int64_t> sizes(int64_t k) const { return batched ? std::vector<int64_t>{B, k} : std::vector<int64_t>{k}; }
+  bool rows(const at::Tensor& t) const { return t.dim() == (batched ? 2 : 1) && t.size(-1) == n && (!batched || t.size(0) == B); }
+};
+
+RunShape run_shape(const at::Tensor& obj, const char* who) {
+  TORCH_CHECK(obj.dim() == 2 || obj.dim() == 3, who, ": obj float32 (n, m) or (B, n, m)");
+  const bool batched = obj.dim() == 3;
+  const RunShape s{batched ? obj.size(0) : 1, obj.size(-2), obj.size(-1), batched};
+  // grid.y of the fitness kernels; the removal kernels have the run on grid.x and share the limit so that the four ops agree
+  TORCH_CHECK(s.B >= 1 && s.B <= EVX_MAX_RUNS, who, ": 1 <= B <= ", EVX_MAX_RUNS, " runs in one launch");
+  return s;
+}
+
 std::vector<at::Tensor> ibea_fitness(const at::Tensor& obj, double kappa) {
   CHECK_DEV(obj); CHECK_F32(obj); CHECK_CONTIG(obj);
-  TORCH_CHECK(obj.dim() == 2, "ibea_fitness: obj float32 (n, m)");
-  const int64_t n = obj.size(0), m = obj.size(1);
-  TORCH_CHECK(m >= 1 && m <= evx_ibea_max_m(), "ibea_fitness: 1 <= m <= ", evx_ibea_max_m());
-  TORCH_CHECK(n <= (1 << 24), "ibea_fitness: n <= 2^24");
+  const RunShape r = run_shape(obj, "ibea_fitness");
+  TORCH_CHECK(r.m >= 1 && r.m <= evx_ibea_max_m(), "ibea_fitness: 1 <= m <= ", evx_ibea_max_m());
+  TORCH_CHECK(r.n <= (1 << 24), "ibea_fitness: n <= 2^24");
   c10::DeviceGuard g(obj.device());
-  auto f = at::empty({n}, obj.options()), C = at::empty({n}, obj.options());
-  evx_ibea_fitness(obj.data_ptr<float>(), (int)n, (int)m, (float)kappa, f.data_ptr<float>(), C.data_ptr<float>(), cur_stream());
+  auto f = at::empty(r.sizes(r.n), obj.options()), C = at::empty(r.sizes(r.n), obj.options());
+  evx_ibea_fitness(obj.data_ptr<float>(), (int)r.B, (int)r.n, (int)r.m, (float)kappa, f.data_ptr<float>(), C.data_ptr<float>(),
+                   cur_stream());
   return {f, C};
 }
 
@@ -1737,45 +1755,46 @@ std::vector<at::Tensor> ibea_truncate(const at::Tensor& obj, const at::Tensor& f
                                       int64_t n_keep) {
   CHECK_DEV(obj); CHECK_F32(obj); CHECK_CONTIG(obj); CHECK_DEV(f); CHECK_F32(f); CHECK_CONTIG(f);
   CHECK_DEV(C); CHECK_F32(C); CHECK_CONTIG(C);
-  TORCH_CHECK(obj.dim() == 2, "ibea_truncate: obj float32 (n, m)");
-  const int64_t n = obj.size(0), m = obj.size(1);
-  TORCH_CHECK(f.dim() == 1 && C.dim() == 1 && f.numel() == n && C.numel() == n, "ibea_truncate: f, C float32 (n,)");
+  const RunShape r = run_shape(obj, "ibea_truncate");
+  const int64_t n = r.n, m = r.m;
+  TORCH_CHECK(r.rows(f) && r.rows(C), "ibea_truncate: f, C float32 (n,), or (B, n) with obj (B, n, m)");
   TORCH_CHECK(n >= 1 && n <= evx_ibea_max_n(), "ibea_truncate: 1 <= n <= ", evx_ibea_max_n());
   TORCH_CHECK(m >= 1 && m <= evx_ibea_max_m(), "ibea_truncate: 1 <= m <= ", evx_ibea_max_m());
   TORCH_CHECK(n_remove >= 0 && n_remove <= n, "ibea_truncate: need 0 <= n_remove <= n");
   TORCH_CHECK(n_keep >= 0 && n_keep <= n - n_remove, "ibea_truncate: need 0 <= n_keep <= n - n_remove");
   TORCH_CHECK(f.device() == obj.device() && C.device() == obj.device(), "ibea_truncate: one device");
   c10::DeviceGuard g(obj.device());
-  auto idx = at::empty({n_keep}, obj.options().dtype(at::kLong)), order = at::empty({n_remove}, obj.options().dtype(at::kLong));
-  const at::Tensor objT = obj.t().contiguous();  // (m, n): a thread's rows are n-strided, its loads coalesced
-  evx_ibea_truncate(objT.data_ptr<float>(), f.data_ptr<float>(), C.data_ptr<float>(), (float)kappa, (int)n, (int)m, (int)n_remove,
-                    (int)n_keep, idx.data_ptr<int64_t>(), order.data_ptr<int64_t>(), cur_stream());
+  const auto i64 = obj.options().dtype(at::kLong);
+  auto idx = at::empty(r.sizes(n_keep), i64), order = at::empty(r.sizes(n_remove), i64);
+  const at::Tensor objT = obj.transpose(-1, -2).contiguous();  // (m, n) per run: a thread's rows are n-strided, its loads coalesced
+  evx_ibea_truncate(objT.data_ptr<float>(), f.data_ptr<float>(), C.data_ptr<float>(), (float)kappa, (int)r.B, (int)n, (int)m,
+                    (int)n_remove, (int)n_keep, idx.data_ptr<int64_t>(), order.data_ptr<int64_t>(), cur_stream());
   return {idx, order};
 }
 
 // sig, S, R, D, nd, msk, nn_d2, nn_idx of spea2_select.hip's two fitness launches
 std::vector<at::Tensor> spea2_fitness(const at::Tensor& obj) {
   CHECK_DEV(obj); CHECK_F32(obj); CHECK_CONTIG(obj);
-  TORCH_CHECK(obj.dim() == 2, "spea2_fitness: obj float32 (n, m)");
-  const int64_t n = obj.size(0), m = obj.size(1);
-  TORCH_CHECK(m >= 1 && m <= evx_spea2_max_m(), "spea2_fitness: 1 <= m <= ", evx_spea2_max_m());
-  TORCH_CHECK(n >= 1 && n <= evx_spea2_fitness_max_n(), "spea2_fitness: 1 <= n <= ", evx_spea2_fitness_max_n());
+  const RunShape r = run_shape(obj, "spea2_fitness");
+  TORCH_CHECK(r.m >= 1 && r.m <= evx_spea2_max_m(), "spea2_fitness: 1 <= m <= ", evx_spea2_max_m());
+  TORCH_CHECK(r.n >= 1 && r.n <= evx_spea2_fitness_max_n(), "spea2_fitness: 1 <= n <= ", evx_spea2_fitness_max_n());
   c10::DeviceGuard g(obj.device());
   const auto f = obj.options(), i32 = obj.options().dtype(at::kInt), b8 = obj.options().dtype(at::kBool);
-  auto S = at::empty({n}, i32), nn_idx = at::empty({n}, i32), nd = at::empty({n}, b8), msk = at::empty({n}, b8);
-  auto D = at::empty({n}, f), R = at::empty({n}, f), sig = at::empty({n}, f), nn_d2 = at::empty({n}, f);
-  evx_spea2_fitness(obj.data_ptr<float>(), (int)n, (int)m, S.data_ptr<int32_t>(), (uint8_t*)nd.data_ptr<bool>(),
+  const auto sz = r.sizes(r.n);
+  auto S = at::empty(sz, i32), nn_idx = at::empty(sz, i32), nd = at::empty(sz, b8), msk = at::empty(sz, b8);
+  auto D = at::empty(sz, f), R = at::empty(sz, f), sig = at::empty(sz, f), nn_d2 = at::empty(sz, f);
+  evx_spea2_fitness(obj.data_ptr<float>(), (int)r.B, (int)r.n, (int)r.m, S.data_ptr<int32_t>(), (uint8_t*)nd.data_ptr<bool>(),
                     (uint8_t*)msk.data_ptr<bool>(), D.data_ptr<float>(), R.data_ptr<float>(), sig.data_ptr<float>(),
                     nn_d2.data_ptr<float>(), nn_idx.data_ptr<int32_t>(), cur_stream());
   return {sig, S, R, D, nd, msk, nn_d2, nn_idx};
 }
 
-// (M, n): the transpose zero padded to the removal kernels' compile-time objective counts, M = evx_padded_m(m).  A thread's rows are
-// n-strided and its loads coalesced; zero rows add nothing to a squared distance
+// (M, n), or (B, M, n) of obj (B, n, m): the transpose zero padded to the removal kernels' compile-time objective counts, M =
+// evx_padded_m(m).  A thread's rows are n-strided and its loads coalesced; zero rows add nothing to a squared distance
 at::Tensor padded_transpose(const at::Tensor& obj) {
-  const int64_t n = obj.size(0), m = obj.size(1), M = evx_padded_m((int)m);
-  auto objT = at::zeros({M, n}, obj.options());
-  objT.narrow(0, 0, m).copy_(obj.t());
+  const int64_t n = obj.size(-2), m = obj.size(-1), M = evx_padded_m((int)m);
+  auto objT = at::zeros(obj.dim() == 3 ? std::vector<int64_t>{obj.size(0), M, n} : std::vector<int64_t>{M, n}, obj.options());
+  objT.narrow(-2, 0, m).copy_(obj.transpose(-1, -2));
   return objT;
 }
 
@@ -1783,9 +1802,9 @@ at::Tensor padded_transpose(const at::Tensor& obj) {
 std::vector<at::Tensor> spea2_truncate(const at::Tensor& obj, const at::Tensor& mask, int64_t n_keep,
                                        const c10::optional<at::Tensor>& nn_d2, const c10::optional<at::Tensor>& nn_idx) {
   CHECK_DEV(obj); CHECK_F32(obj); CHECK_CONTIG(obj); CHECK_DEV(mask); CHECK_CONTIG(mask);
-  TORCH_CHECK(obj.dim() == 2, "spea2_truncate: obj float32 (n, m)");
-  const int64_t n = obj.size(0), m = obj.size(1);
-  TORCH_CHECK(mask.scalar_type() == at::kBool && mask.dim() == 1 && mask.numel() == n, "spea2_truncate: mask bool (n,)");
+  const RunShape r = run_shape(obj, "spea2_truncate");
+  const int64_t n = r.n, m = r.m;
+  TORCH_CHECK(mask.scalar_type() == at::kBool && r.rows(mask), "spea2_truncate: mask bool (n,), or (B, n) with obj (B, n, m)");
   TORCH_CHECK(n >= 1 && n <= evx_spea2_max_n(), "spea2_truncate: 1 <= n <= ", evx_spea2_max_n());
   TORCH_CHECK(m >= 1 && m <= evx_spea2_max_m(), "spea2_truncate: 1 <= m <= ", evx_spea2_max_m());
   TORCH_CHECK(n_keep >= 1, "spea2_truncate: need n_keep >= 1");
@@ -1797,22 +1816,22 @@ std::vector<at::Tensor> spea2_truncate(const at::Tensor& obj, const at::Tensor& 
     d2v = *nn_d2;
     idxv = *nn_idx;
     CHECK_DEV(d2v); CHECK_F32(d2v); CHECK_CONTIG(d2v); CHECK_DEV(idxv); CHECK_CONTIG(idxv);
-    TORCH_CHECK(d2v.dim() == 1 && d2v.numel() == n, "spea2_truncate: nn_d2 float32 (n,)");
-    TORCH_CHECK(idxv.scalar_type() == at::kInt && idxv.dim() == 1 && idxv.numel() == n, "spea2_truncate: nn_idx int32 (n,)");
+    TORCH_CHECK(r.rows(d2v), "spea2_truncate: nn_d2 float32 (n,), or (B, n) with obj (B, n, m)");
+    TORCH_CHECK(idxv.scalar_type() == at::kInt && r.rows(idxv), "spea2_truncate: nn_idx int32 (n,), or (B, n) with obj (B, n, m)");
     TORCH_CHECK(d2v.device() == obj.device() && idxv.device() == obj.device(), "spea2_truncate: one device");
   } else {
-    d2v = at::empty({n}, obj.options());
-    idxv = at::empty({n}, obj.options().dtype(at::kInt));
-    evx_spea2_neighbours(obj.data_ptr<float>(), (int)n, (int)m, (const uint8_t*)mask.data_ptr<bool>(), d2v.data_ptr<float>(),
+    d2v = at::empty(r.sizes(n), obj.options());
+    idxv = at::empty(r.sizes(n), obj.options().dtype(at::kInt));
+    evx_spea2_neighbours(obj.data_ptr<float>(), (int)r.B, (int)n, (int)m, (const uint8_t*)mask.data_ptr<bool>(), d2v.data_ptr<float>(),
                          idxv.data_ptr<int32_t>(), cur_stream());
   }
   const int64_t n_order = std::max<int64_t>(n - n_keep, 0);
   const at::Tensor objT = padded_transpose(obj);
-  auto keep = at::empty({n}, obj.options().dtype(at::kBool)), order = at::empty({n_order}, obj.options().dtype(at::kLong));
-  auto stats = at::empty({2}, obj.options().dtype(at::kInt));
-  evx_spea2_truncate(objT.data_ptr<float>(), (int)n, (int)objT.size(0), (const uint8_t*)mask.data_ptr<bool>(), d2v.data_ptr<float>(),
-                     idxv.data_ptr<int32_t>(), (int)n_keep, (uint8_t*)keep.data_ptr<bool>(), order.data_ptr<int64_t>(), (int)n_order,
-                     stats.data_ptr<int32_t>(), cur_stream());
+  auto keep = at::empty(r.sizes(n), obj.options().dtype(at::kBool)), order = at::empty(r.sizes(n_order), obj.options().dtype(at::kLong));
+  auto stats = at::empty(r.sizes(2), obj.options().dtype(at::kInt));
+  evx_spea2_truncate(objT.data_ptr<float>(), (int)r.B, (int)n, (int)objT.size(-2), (const uint8_t*)mask.data_ptr<bool>(),
+                     d2v.data_ptr<float>(), idxv.data_ptr<int32_t>(), (int)n_keep, (uint8_t*)keep.data_ptr<bool>(),
+                     order.data_ptr<int64_t>(), (int)n_order, stats.data_ptr<int32_t>(), cur_stream());
   return {keep, order, stats};
 }
 

@@ -292,26 +292,32 @@ int evx_sra_rank_max_n();
 int evx_sra_indicators_max_m();
 void evx_sra_rank(const float* I1, const float* I2, const float* u, const float* pc, int n, int64_t* rank, hipStream_t s);
 void evx_sra_indicators(const float* obj, int n, int m, float* I1, float* I2, hipStream_t s);
+// ibea_select.hip and spea2_select.hip take B independent runs in one launch: every array gains a leading run axis (obj (B, n, m),
+// per-row arrays (B, n), …), the fitness kernels put the run on grid.y and the removal kernels run one workgroup per run.  B = 1 is
+// a single population.
+constexpr int EVX_MAX_RUNS = 65535;  // grid.y
 // ibea_select.hip: IBEA's I_ε+ fitness (f, C of the normalised objectives, m ≤ evx_ibea_max_m()) and its truncation
-// (objT the (m, n) transpose, n ≤ evx_ibea_max_n(), n_keep ≤ n − n_remove; idx (n_keep,) ascending survivors, order (n_remove,) the removed rows)
+// (objT the (m, n) transposes, n ≤ evx_ibea_max_n(), n_keep ≤ n − n_remove, both shared by the runs; idx (n_keep,) ascending survivors,
+// order (n_remove,) the removed rows)
 int evx_ibea_max_n();
 int evx_ibea_max_m();
-void evx_ibea_fitness(const float* obj, int n, int m, float kappa, float* f, float* C, hipStream_t s);
-void evx_ibea_truncate(const float* objT, const float* f, const float* C, float kappa, int n, int m, int n_remove, int n_keep,
+void evx_ibea_fitness(const float* obj, int B, int n, int m, float kappa, float* f, float* C, hipStream_t s);
+void evx_ibea_truncate(const float* objT, const float* f, const float* C, float kappa, int B, int n, int m, int n_remove, int n_keep,
                        int64_t* idx, int64_t* order, hipStream_t s);
 // the objective counts the one-workgroup removal kernels (spea2_select.hip, bce_select.hip) are compiled for: m is zero padded to this
 inline int evx_padded_m(int m) { return m <= 2 ? 2 : m == 3 ? 3 : m == 4 ? 4 : m <= 8 ? 8 : 16; }
 // spea2_select.hip: SPEA2's fitness in two launches (n ≤ evx_spea2_fitness_max_n(), m ≤ evx_spea2_max_m(): S, nd, msk = nd without NaN rows,
 // D, R, sig = D + R and the nearest neighbour (nn_d2, nn_idx) of every row of msk among the others), the neighbour pass alone for a given mask,
-// and the truncation on one workgroup (objT the (M, n) transpose zero padded to M = evx_padded_m(m) rows, n ≤ evx_spea2_max_n();
-// keep (n,) the masked rows that stay, order (n_order,) the removed rows then −1, stats = {rescans, removed})
+// and the truncation on one workgroup per run (objT the (M, n) transposes zero padded to M = evx_padded_m(m) rows, n ≤ evx_spea2_max_n();
+// keep (n,) the masked rows that stay, order (n_order,) the removed rows then −1, stats = {rescans, removed} of each run; n_keep is shared,
+// the number of rows removed is each run's own)
 int evx_spea2_max_n();
 int evx_spea2_fitness_max_n();
 int evx_spea2_max_m();
-void evx_spea2_fitness(const float* obj, int n, int m, int32_t* S, uint8_t* nd, uint8_t* msk, float* D, float* R, float* sig,
+void evx_spea2_fitness(const float* obj, int B, int n, int m, int32_t* S, uint8_t* nd, uint8_t* msk, float* D, float* R, float* sig,
                        float* nn_d2, int32_t* nn_idx, hipStream_t s);
-void evx_spea2_neighbours(const float* obj, int n, int m, const uint8_t* mask, float* nn_d2, int32_t* nn_idx, hipStream_t s);
-void evx_spea2_truncate(const float* objT, int n, int M, const uint8_t* mask, const float* nn_d2, const int32_t* nn_idx, int n_keep,
+void evx_spea2_neighbours(const float* obj, int B, int n, int m, const uint8_t* mask, float* nn_d2, int32_t* nn_idx, hipStream_t s);
+void evx_spea2_truncate(const float* objT, int B, int n, int M, const uint8_t* mask, const float* nn_d2, const int32_t* nn_idx, int n_keep,
                         uint8_t* keep, int64_t* order, int n_order, int32_t* stats, hipStream_t s);
 // bce_select.hip: BCE-IBEA's PC selection and exploration (objT the (M, n) transpose zero padded to M = evx_padded_m(m) rows;
 // ws evx_bce_ws_floats() floats: the spans and, last, the niche radius; cnt one word, the rows of the mask).  evx_bce_mask: the rows no

@@ -39,19 +39,19 @@
 //
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
 //   kernel                     VGPR  SGPR  scratch  LDS [B]
-//   ibea_fitness               62    56    0        17664
-//   ibea_truncate<1, m = 2>    46    69    0        2896
-//   ibea_truncate<1, m = 3>    49    67    0        2896
-//   ibea_truncate<1, any m>    47    76    0        2896
-//   ibea_truncate<2, m = 2>    52    71    0        2960
-//   ibea_truncate<2, m = 3>    56    69    0        2960
-//   ibea_truncate<2, any m>    51    96    0        2960
+//   ibea_fitness               62    60    0        17664
+//   ibea_truncate<1, m = 2>    46    70    0        2896
+//   ibea_truncate<1, m = 3>    49    68    0        2896
+//   ibea_truncate<1, any m>    47    77    0        2896
+//   ibea_truncate<2, m = 2>    52    72    0        2960
+//   ibea_truncate<2, m = 3>    56    70    0        2960
+//   ibea_truncate<2, any m>    51    98    0        2960
 //   ibea_truncate<4, m = 2>    63    92    0        3088
-//   ibea_truncate<4, m = 3>    55    65    0        3088
-//   ibea_truncate<4, any m>    63    100   0        3088
-//   ibea_truncate<8, m = 2>    78    81    0        3344
-//   ibea_truncate<8, m = 3>    86    81    0        3344
-//   ibea_truncate<8, any m>    105   106   0        3344
+//   ibea_truncate<4, m = 3>    55    66    0        3088
+//   ibea_truncate<4, any m>    63    102   0        3088
+//   ibea_truncate<8, m = 2>    78    82    0        3344
+//   ibea_truncate<8, m = 3>    86    82    0        3344
+//   ibea_truncate<8, any m>    78    83    0        3344
 // No spill: 1024 threads are four waves per SIMD, 128 VGPRs each.
 #include "evoxmi_mo.h"
 
@@ -71,6 +71,10 @@ __global__ void __launch_bounds__(IF_THREADS) ibea_fitness_kernel(const float* _
                                                                    float* __restrict__ f, float* __restrict__ C) {
   __shared__ float is[IF_TILE * (IB_MAX_M + 1)];
   __shared__ float js[IF_WAVES][IB_MAX_M];
+  const int64_t run = blockIdx.y;  // obj (B, n, m), f and C (B, n): the run's slices from here on
+  obj += run * n * m;
+  f += run * n;
+  C += run * n;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = blockIdx.x * IF_WAVES + wave;
   const int ms = m | 1;  // odd row stride
@@ -118,7 +122,8 @@ __device__ __forceinline__ unsigned long long arg_key(float v, int i) {
 }
 
 // MR > 0: m == MR and the thread's objective rows live in registers; MR == 0: any m, re-read each step.
-// oT is the (m, n) transpose of the objectives; blockDim.x = 2^lg.
+// oT is the (m, n) transpose of the objectives; blockDim.x = 2^lg.  A workgroup per run: blockIdx.x is the run, oT (B, m, n),
+// f0 and C (B, n), idx (B, n_keep), order (B, n_remove); the runs share nothing.
 template <int IT, int MR>
 __global__ void __launch_bounds__(IB_THREADS) ibea_truncate_kernel(const float* __restrict__ oT, const float* __restrict__ f0,
                                                                     const float* __restrict__ C, float kappa, int n, int m, int lg,
@@ -127,6 +132,12 @@ __global__ void __launch_bounds__(IB_THREADS) ibea_truncate_kernel(const float* 
   __shared__ IbPart part[2][IB_WAVES];
   __shared__ float rows[2][IB_WAVES + 1][IB_MAX_M + 1];  // a candidate's m objectives, then its C; slot 16: row x again
   __shared__ int wsum[IT][IB_WAVES];
+  const int64_t run = blockIdx.x;
+  oT += run * m * n;
+  f0 += run * n;
+  C += run * n;
+  idx += run * n_keep;
+  order += run * n_remove;
   const int r = threadIdx.x, lane = r & 63, wave = r >> 6, nt = 1 << lg, nw = nt >> 6;
   constexpr int MRR = MR > 0 ? MR : 1;
   const float inf = __int_as_float(0x7f800000);
@@ -253,14 +264,14 @@ __global__ void __launch_bounds__(IB_THREADS) ibea_truncate_kernel(const float* 
 }
 
 template <int IT>
-void launch_truncate(int lg, const float* oT, const float* f, const float* C, float kappa, int n, int m, int n_remove, int n_keep,
+void launch_truncate(int lg, int B, const float* oT, const float* f, const float* C, float kappa, int n, int m, int n_remove, int n_keep,
                      int64_t* idx, int64_t* order, hipStream_t s) {
   if (m == 2)
-    ibea_truncate_kernel<IT, 2><<<1, 1 << lg, 0, s>>>(oT, f, C, kappa, n, m, lg, n_remove, n_keep, idx, order);
+    ibea_truncate_kernel<IT, 2><<<B, 1 << lg, 0, s>>>(oT, f, C, kappa, n, m, lg, n_remove, n_keep, idx, order);
   else if (m == 3)
-    ibea_truncate_kernel<IT, 3><<<1, 1 << lg, 0, s>>>(oT, f, C, kappa, n, m, lg, n_remove, n_keep, idx, order);
+    ibea_truncate_kernel<IT, 3><<<B, 1 << lg, 0, s>>>(oT, f, C, kappa, n, m, lg, n_remove, n_keep, idx, order);
   else
-    ibea_truncate_kernel<IT, 0><<<1, 1 << lg, 0, s>>>(oT, f, C, kappa, n, m, lg, n_remove, n_keep, idx, order);
+    ibea_truncate_kernel<IT, 0><<<B, 1 << lg, 0, s>>>(oT, f, C, kappa, n, m, lg, n_remove, n_keep, idx, order);
 }
 
 }  // namespace
@@ -268,21 +279,21 @@ void launch_truncate(int lg, const float* oT, const float* f, const float* C, fl
 int evx_ibea_max_n() { return IB_MAX_N; }
 int evx_ibea_max_m() { return IB_MAX_M; }
 
-void evx_ibea_fitness(const float* obj, int n, int m, float kappa, float* f, float* C, hipStream_t s) {
-  if (n <= 0) return;
-  ibea_fitness_kernel<<<(n + IF_WAVES - 1) / IF_WAVES, IF_THREADS, 0, s>>>(obj, n, m, kappa, f, C);
+void evx_ibea_fitness(const float* obj, int B, int n, int m, float kappa, float* f, float* C, hipStream_t s) {
+  if (n <= 0 || B < 1 || B > EVX_MAX_RUNS) return;
+  ibea_fitness_kernel<<<dim3((n + IF_WAVES - 1) / IF_WAVES, B), IF_THREADS, 0, s>>>(obj, n, m, kappa, f, C);
 }
 
-void evx_ibea_truncate(const float* oT, const float* f, const float* C, float kappa, int n, int m, int n_remove, int n_keep,
+void evx_ibea_truncate(const float* oT, const float* f, const float* C, float kappa, int B, int n, int m, int n_remove, int n_keep,
                        int64_t* idx, int64_t* order, hipStream_t s) {
-  if (n <= 0 || n > IB_MAX_N || m < 1 || m > IB_MAX_M) return;
+  if (n <= 0 || n > IB_MAX_N || m < 1 || m > IB_MAX_M || B < 1 || B > EVX_MAX_RUNS) return;
   // four waves (one per SIMD) while eight rows per thread suffice, then more waves
   if (n <= 256)
-    launch_truncate<1>(8, oT, f, C, kappa, n, m, n_remove, n_keep, idx, order, s);
+    launch_truncate<1>(8, B, oT, f, C, kappa, n, m, n_remove, n_keep, idx, order, s);
   else if (n <= 512)
-    launch_truncate<2>(8, oT, f, C, kappa, n, m, n_remove, n_keep, idx, order, s);
+    launch_truncate<2>(8, B, oT, f, C, kappa, n, m, n_remove, n_keep, idx, order, s);
   else if (n <= 1024)
-    launch_truncate<4>(8, oT, f, C, kappa, n, m, n_remove, n_keep, idx, order, s);
+    launch_truncate<4>(8, B, oT, f, C, kappa, n, m, n_remove, n_keep, idx, order, s);
   else
-    launch_truncate<8>(n <= 2048 ? 8 : n <= 4096 ? 9 : 10, oT, f, C, kappa, n, m, n_remove, n_keep, idx, order, s);
+    launch_truncate<8>(n <= 2048 ? 8 : n <= 4096 ? 9 : 10, B, oT, f, C, kappa, n, m, n_remove, n_keep, idx, order, s);
 }

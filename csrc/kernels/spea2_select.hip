@@ -41,38 +41,38 @@
 //
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
 //   kernel <IT, M, T>              VGPR  SGPR  scratch  LDS [B]
-//   spea2_fit1                     62    106   0        17664
-//   spea2_fit2                     31    84    0        18944
-//   spea2_truncate<1, 2, 256>      62    61    0        17184
-//   spea2_truncate<1, 3, 256>      64    65    0        17184
-//   spea2_truncate<1, 4, 256>      66    75    0        17184
-//   spea2_truncate<1, 8, 256>      58    76    0        16928
-//   spea2_truncate<1, 16, 256>     95    94    0        16928
-//   spea2_truncate<2, 2, 256>      66    65    0        17184
-//   spea2_truncate<2, 3, 256>      62    69    0        17184
-//   spea2_truncate<2, 4, 256>      65    81    0        17184
-//   spea2_truncate<2, 8, 256>      72    82    0        16928
-//   spea2_truncate<2, 16, 256>     130   100   0        16928
-//   spea2_truncate<4, 2, 256>      80    75    0        17184
-//   spea2_truncate<4, 3, 256>      95    78    0        17184
-//   spea2_truncate<4, 4, 256>      73    93    0        17184
-//   spea2_truncate<4, 8, 256>      88    94    0        16928
-//   spea2_truncate<4, 16, 256>     159   106   0        16928
-//   spea2_truncate<8, 2, 256>      122   93    0        17184
-//   spea2_truncate<8, 3, 256>      157   104   0        17184
+//   spea2_fit1                     63    106   0        17664
+//   spea2_fit2                     31    86    0        18944
+//   spea2_truncate<1, 2, 256>      62    69    0        17184
+//   spea2_truncate<1, 3, 256>      64    73    0        17184
+//   spea2_truncate<1, 4, 256>      66    83    0        17184
+//   spea2_truncate<1, 8, 256>      58    84    0        16928
+//   spea2_truncate<1, 16, 256>     96    100   0        16928
+//   spea2_truncate<2, 2, 256>      66    75    0        17184
+//   spea2_truncate<2, 3, 256>      62    77    0        17184
+//   spea2_truncate<2, 4, 256>      65    89    0        17184
+//   spea2_truncate<2, 8, 256>      72    90    0        16928
+//   spea2_truncate<2, 16, 256>     132   106   0        16928
+//   spea2_truncate<4, 2, 256>      80    83    0        17184
+//   spea2_truncate<4, 3, 256>      95    86    0        17184
+//   spea2_truncate<4, 4, 256>      73    101   0        17184
+//   spea2_truncate<4, 8, 256>      88    102   0        16928
+//   spea2_truncate<4, 16, 256>     160   106   0        16928
+//   spea2_truncate<8, 2, 256>      122   101   0        17184
+//   spea2_truncate<8, 3, 256>      158   106   0        17184
 //   spea2_truncate<8, 4, 256>      127   106   0        17184
 //   spea2_truncate<8, 8, 256>      244   106   0        16928
-//   spea2_truncate<8, 16, 256>     170   105   0        16928
-//   spea2_truncate<8, 2, 512>      155   100   0        17184
+//   spea2_truncate<8, 16, 256>     173   106   0        16928
+//   spea2_truncate<8, 2, 512>      155   106   0        17184
 //   spea2_truncate<8, 3, 512>      158   106   0        17184
 //   spea2_truncate<8, 4, 512>      169   106   0        17184
 //   spea2_truncate<8, 8, 512>      216   106   0        16928
-//   spea2_truncate<8, 16, 512>     170   106   0        16928
+//   spea2_truncate<8, 16, 512>     173   106   0        16928
 //   spea2_truncate<16, 2, 512>     221   106   0        16928
 //   spea2_truncate<16, 3, 512>     253   106   0        16928
-//   spea2_truncate<16, 4, 512>     129   92    0        16928
-//   spea2_truncate<16, 8, 512>     170   99    0        16928
-//   spea2_truncate<16, 16, 512>    193   102   0        16928
+//   spea2_truncate<16, 4, 512>     129   100   0        16928
+//   spea2_truncate<16, 8, 512>     170   106   0        16928
+//   spea2_truncate<16, 16, 512>    196   106   0        16928
 // 256 threads are one wave per SIMD, 512 threads two (256 VGPRs each): no spill.
 #include "evoxmi_mo.h"
 
@@ -110,6 +110,12 @@ __global__ void __launch_bounds__(SF_THREADS) spea2_fit1_kernel(const float* __r
                                                                  float* __restrict__ D) {
   __shared__ float is[SF_TILE * (SP_MAX_M + 1)];
   __shared__ float js[SF_WAVES][SP_MAX_M];
+  const int64_t run = blockIdx.y;  // obj (B, n, m), the outputs (B, n): the run's slices from here on
+  obj += run * n * m;
+  S += run * n;
+  nd += run * n;
+  msk += run * n;
+  D += run * n;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = blockIdx.x * SF_WAVES + wave;
   const int ms = m | 1;
@@ -171,13 +177,24 @@ __global__ void __launch_bounds__(SF_THREADS) spea2_fit2_kernel(const float* __r
   __shared__ float js[SF_WAVES][SP_MAX_M];
   __shared__ int32_t ss[SF_TILE];
   __shared__ uint8_t mk[SF_TILE];
+  const bool fit = S != nullptr;
+  const int64_t run = blockIdx.y;  // as in spea2_fit1_kernel
+  obj += run * n * m;
+  msk += run * n;
+  nn_d2 += run * n;
+  nn_idx += run * n;
+  if (fit) {
+    S += run * n;
+    D += run * n;
+    R += run * n;
+    sig += run * n;
+  }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = blockIdx.x * SF_WAVES + wave;
   const int ms = m | 1;
   const float inf = __uint_as_float(SP_INF);
   if (lane < m) js[wave][lane] = r < n ? obj[(int64_t)r * m + lane] : 0.f;
   const bool masked = r < n && msk[r] != 0;
-  const bool fit = S != nullptr;
   const float* orow = js[wave];
 
   uint32_t racc = 0u;
@@ -219,7 +236,9 @@ __global__ void __launch_bounds__(SF_THREADS) spea2_fit2_kernel(const float* __r
   }
 }
 
-// oT: the objectives transposed and zero padded to (M, n); blockDim.x = TB; order has n_order entries
+// oT: the objectives transposed and zero padded to (M, n); blockDim.x = TB; order has n_order entries.  A workgroup per run:
+// blockIdx.x is the run, oT (B, M, n), mask, nn_d2, nn_idx and keep (B, n), order (B, n_order), stats (B, 2); every run counts
+// its own k and the runs share nothing.
 template <int IT, int M, int TB>
 __global__ void __launch_bounds__(TB) spea2_truncate_kernel(const float* __restrict__ oT, const uint8_t* __restrict__ mask,
                                                             const float* __restrict__ nn_d2, const int32_t* __restrict__ nn_idx, int n,
@@ -234,6 +253,14 @@ __global__ void __launch_bounds__(TB) spea2_truncate_kernel(const float* __restr
   __shared__ int wcount[SP_WAVES];
   using Shape = evx::RemovalShape<TB>;
   constexpr int lg = Shape::lg, nt = Shape::nt, nw = Shape::nw;
+  const int64_t run = blockIdx.x;
+  oT += run * M * n;
+  mask += run * n;
+  nn_d2 += run * n;
+  nn_idx += run * n;
+  keep += run * n;
+  order += run * n_order;
+  stats += run * 2;
   const int r = threadIdx.x, lane = r & 63, wave = r >> 6;
   const float inf = __uint_as_float(SP_INF);
   const unsigned long long below = (1ull << lane) - 1ull;
@@ -385,27 +412,27 @@ int evx_spea2_max_n() { return SP_MAX_N; }
 int evx_spea2_fitness_max_n() { return SP_FIT_MAX_N; }
 int evx_spea2_max_m() { return SP_MAX_M; }
 
-void evx_spea2_fitness(const float* obj, int n, int m, int32_t* S, uint8_t* nd, uint8_t* msk, float* D, float* R, float* sig,
+void evx_spea2_fitness(const float* obj, int B, int n, int m, int32_t* S, uint8_t* nd, uint8_t* msk, float* D, float* R, float* sig,
                        float* nn_d2, int32_t* nn_idx, hipStream_t s) {
-  if (n <= 0 || n > SP_FIT_MAX_N || m < 1 || m > SP_MAX_M) return;
-  const int grid = (n + SF_WAVES - 1) / SF_WAVES;
+  if (n <= 0 || n > SP_FIT_MAX_N || m < 1 || m > SP_MAX_M || B < 1 || B > EVX_MAX_RUNS) return;
+  const dim3 grid((n + SF_WAVES - 1) / SF_WAVES, B);
   spea2_fit1_kernel<<<grid, SF_THREADS, 0, s>>>(obj, n, m, S, nd, msk, D);
   spea2_fit2_kernel<<<grid, SF_THREADS, 0, s>>>(obj, n, m, S, msk, D, R, sig, nn_d2, nn_idx);
 }
 
-void evx_spea2_neighbours(const float* obj, int n, int m, const uint8_t* mask, float* nn_d2, int32_t* nn_idx, hipStream_t s) {
-  if (n <= 0 || m < 1 || m > SP_MAX_M) return;
-  spea2_fit2_kernel<<<(n + SF_WAVES - 1) / SF_WAVES, SF_THREADS, 0, s>>>(obj, n, m, nullptr, mask, nullptr, nullptr, nullptr, nn_d2,
-                                                                         nn_idx);
+void evx_spea2_neighbours(const float* obj, int B, int n, int m, const uint8_t* mask, float* nn_d2, int32_t* nn_idx, hipStream_t s) {
+  if (n <= 0 || m < 1 || m > SP_MAX_M || B < 1 || B > EVX_MAX_RUNS) return;
+  spea2_fit2_kernel<<<dim3((n + SF_WAVES - 1) / SF_WAVES, B), SF_THREADS, 0, s>>>(obj, n, m, nullptr, mask, nullptr, nullptr, nullptr,
+                                                                                  nn_d2, nn_idx);
 }
 
-void evx_spea2_truncate(const float* objT, int n, int M, const uint8_t* mask, const float* nn_d2, const int32_t* nn_idx, int n_keep,
+void evx_spea2_truncate(const float* objT, int B, int n, int M, const uint8_t* mask, const float* nn_d2, const int32_t* nn_idx, int n_keep,
                         uint8_t* keep, int64_t* order, int n_order, int32_t* stats, hipStream_t s) {
-  if (n <= 0 || n > SP_MAX_N || M != evx_padded_m(M)) return;
+  if (n <= 0 || n > SP_MAX_N || M != evx_padded_m(M) || B < 1 || B > EVX_MAX_RUNS) return;
   evx::dispatch_removal_shape(n, [&](auto it, auto tb) {
     evx::dispatch_padded_m(M, [&](auto mm) {
       constexpr int IT = decltype(it)::value, TB = decltype(tb)::value, MM = decltype(mm)::value;
-      spea2_truncate_kernel<IT, MM, TB><<<1, TB, 0, s>>>(objT, mask, nn_d2, nn_idx, n, n_keep, keep, order, n_order, stats);
+      spea2_truncate_kernel<IT, MM, TB><<<B, TB, 0, s>>>(objT, mask, nn_d2, nn_idx, n, n_keep, keep, order, n_order, stats);
     });
   });
 }

@@ -20,9 +20,18 @@ batched forms with one workgroup (or one grid row) per run (``nds_batched.hip``,
 ``evo_ops.hip``), for merged populations of at most 8192 rows and 8 objectives per run; above those
 caps the batched step raises ``NotImplementedError`` instead of falling back to one launch per run.
 On the CPU their environmental selection, which has data-dependent control flow, runs run by run
-inside one op (``evoxmi.ops.nds.nsga2_survivors_torch``).  The other multi-objective algorithms are not
-covered: their selections read the host or loop on data, and ``BatchedRuns`` over them still raises
-from ``vmap`` (data-dependent control flow, ``.item()``).
+inside one op (``evoxmi.ops.nds.nsga2_survivors_torch``).
+
+IBEA and SPEA2 batch too (``tests/test_batched_ibea_spea2.py``, ``tests/test_batched_ibea_spea2_gpu.py``).  Every
+kernel of ``ibea_select.hip`` and ``spea2_select.hip`` takes a run index: the fitness passes put the run on the grid
+and the removal loops, which run in one workgroup, get a workgroup per run, so R loops run at once on R compute
+units (merged populations of at most 8192 rows and 16 objectives per run; above that the batched step raises
+``NotImplementedError``).  SPEA2's runs each count their own removals.  On the CPU SPEA2's fitness and selection
+run run by run inside Python-registered ops (``evoxmi.ops.spea2``); IBEA's torch path is traced by ``vmap`` itself.
+
+Covered multi-objective algorithms: NSGA-II, GDE3, IBEA, SPEA2.  The others are not, and an uncovered one is not
+guaranteed to raise.  Most raise from ``vmap`` (their selections read the host or loop on data), but RVEA runs and its
+runs differ from solo runs: do not rely on ``BatchedRuns`` over an algorithm that is not listed here.
 """
 from __future__ import annotations
 

@@ -14,12 +14,16 @@ per run).  Each rule moves the run axis to the front and calls the op's batched 
 * ``sbx`` / ``pm``: x (B, n, d), keys (B, 2, 2) → grid.y = run, run-local row counters, bounds shared
   (``evo_ops.hip``);
 * ``nds``: f (B, n, m) → one workgroup per run (``nds_batched.hip``; n ≤ 8192, m ≤ 8 per run);
-* ``nsga_select``: rank (B, n), f (B, n, m) → one workgroup per run (``nsga_select.hip``).
+* ``nsga_select``: rank (B, n), f (B, n, m) → one workgroup per run (``nsga_select.hip``);
+* ``ibea_fitness`` / ``spea2_fitness``: obj (B, n, m) → grid.y = run (``ibea_select.hip``, ``spea2_select.hip``; m ≤ 16, for
+  SPEA2 n ≤ 32768 per run);
+* ``ibea_truncate`` / ``spea2_truncate``: obj (B, n, m), per-row operands (B, n) → one workgroup per run, whose removal loop
+  is the single-run one (n ≤ 8192, m ≤ 16 per run); SPEA2's runs each count their own removals.
 
 Each run's words/trials are bit-identical to the single-run op with that run's key
 (``tests/test_batched_runs.py``), each run's sorted keys and indices to the op applied row by row
 (``tests/test_kernels_gpu.py``), each run's ranks, survivors and offspring to the single-run ops
-(``tests/test_batched_mo_gpu.py``).  A per-run shape above a batched kernel's cap raises
+(``tests/test_batched_mo_gpu.py``, ``tests/test_batched_ibea_spea2_gpu.py``).  A per-run shape above a batched kernel's cap raises
 ``NotImplementedError``: there is no silent run-by-run fallback.  This mirrors the reference's use of ``jax.vmap`` for
 independent copies of a workflow (``run/run_de.py:54-114`` runs 32 seeds per function).
 """
@@ -119,6 +123,53 @@ def _nsga_select(info, in_dims, rank, f, N, mask_pos):
     return _ext.ops().nsga_select(_front(rank, in_dims[0], B), fb, N, mask_pos), 0
 
 
+def _runs_of(x, bdim, B, per_run_dim, what):
+    """``_front`` of an operand whose per-run form has ``per_run_dim`` dimensions."""
+    xb = _front(x, bdim, B)
+    if xb.dim() != per_run_dim + 1:
+        raise NotImplementedError(f"{what}: a per-run operand has {xb.dim() - 1} dimensions where {per_run_dim} are due")
+    return xb
+
+
+def _ibea_fitness(info, in_dims, obj, kappa):
+    from .ibea import check_batched_caps
+
+    ob = _runs_of(obj, in_dims[0], info.batch_size, 2, "ibea_fitness vmap rule")
+    check_batched_caps(ob.shape[1], ob.shape[2], "ibea_fitness vmap rule", need_rows=False)
+    return list(_ext.ops().ibea_fitness(ob, kappa)), [0, 0]
+
+
+def _ibea_truncate(info, in_dims, obj, f, C, kappa, n_remove, n_keep):
+    from .ibea import check_batched_caps
+
+    B, what = info.batch_size, "ibea_truncate vmap rule"
+    ob = _runs_of(obj, in_dims[0], B, 2, what)
+    check_batched_caps(ob.shape[1], ob.shape[2], what)
+    return list(_ext.ops().ibea_truncate(ob, _runs_of(f, in_dims[1], B, 1, what), _runs_of(C, in_dims[2], B, 1, what), kappa,
+                                         n_remove, n_keep)), [0, 0]
+
+
+def _spea2_fitness(info, in_dims, obj):
+    from .spea2 import FIT_N_CAP, check_batched_caps
+
+    ob = _runs_of(obj, in_dims[0], info.batch_size, 2, "spea2_fitness vmap rule")
+    check_batched_caps(ob.shape[1], ob.shape[2], "spea2_fitness vmap rule", FIT_N_CAP)
+    return list(_ext.ops().spea2_fitness(ob)), [0] * 8
+
+
+def _spea2_truncate(info, in_dims, obj, mask, n_keep, nn_d2=None, nn_idx=None):
+    from .spea2 import check_batched_caps
+
+    B, what = info.batch_size, "spea2_truncate vmap rule"
+    if (nn_d2 is None) != (nn_idx is None):
+        raise NotImplementedError(f"{what}: nn_d2 and nn_idx are given together or not at all")
+    ob = _runs_of(obj, in_dims[0], B, 2, what)
+    check_batched_caps(ob.shape[1], ob.shape[2], what)
+    if nn_d2 is not None:  # in_dims stops at the last argument that was passed
+        nn_d2, nn_idx = _runs_of(nn_d2, in_dims[3], B, 1, what), _runs_of(nn_idx, in_dims[4], B, 1, what)
+    return list(_ext.ops().spea2_truncate(ob, _runs_of(mask, in_dims[1], B, 1, what), n_keep, nn_d2, nn_idx)), [0, 0, 0]
+
+
 def register():
     """Install the rules (idempotent).  Without the compiled extension there is nothing to
     batch: CPU tensors never reach the HIP ops, and a device op raises on its own."""
@@ -126,6 +177,8 @@ def register():
     if _REGISTERED or not _ext.load(build_if_missing=False):
         return
     for name, fn in (("philox_words", _philox_words), ("philox_fill", _philox_fill), ("rank_argsort_f32", _rank_argsort_f32),
-                     ("de_trial", _de_trial), ("sbx", _sbx), ("pm", _pm), ("nds", _nds), ("nsga_select", _nsga_select)):
+                     ("de_trial", _de_trial), ("sbx", _sbx), ("pm", _pm), ("nds", _nds), ("nsga_select", _nsga_select),
+                     ("ibea_fitness", _ibea_fitness), ("ibea_truncate", _ibea_truncate), ("spea2_fitness", _spea2_fitness),
+                     ("spea2_truncate", _spea2_truncate)):
         torch.library.register_vmap(f"evoxmi::{name}", fn)
     _REGISTERED = True

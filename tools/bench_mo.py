@@ -18,13 +18,13 @@
   gde3  : GDE3 pop=4096 on DTLZ2 (m=3, d=500)              — 1×MI355X
   moead : MOEA/D pop=16384 on LSMOP1 (m=3, d=10000), Tchebycheff aggregation
 
-  --runs R (nsga2, gde3): R independent seeds, the protocol of a multi-objective comparison (20–30 runs at
+  --runs R (nsga2, gde3, ibea, spea2): R independent seeds, the protocol of a multi-objective comparison (20–30 runs at
   pop 100–200).  Without --batched the R seeds run one after another, each its own workflow (and hipGraph);
   with --batched they are one BatchedRuns workflow, every launch of a generation advancing all R runs.
   Both modes start run r from split(fold_in(key, 1), R)[r], so they compute the same runs; ms_per_gen is the
   time of one generation of all R runs, and after the timed region every run's IGD is printed.
 
-python tools/bench_mo.py --algo nsga2|gde3 [--pop 100 --dim 12] --runs 32 [--batched]
+python tools/bench_mo.py --algo nsga2|gde3|ibea|spea2 [--pop 100 --dim 12] --runs 32 [--batched]
 python tools/bench_mo.py --algo nsga2|nsga3|sra|ibea|spea2|bceibea|knea|m2m|rvea|rveaa|lmocso|bige|tdea|moead [--gens 20] [--warmup 3] [--no-graph]
 torchrun --nproc-per-node 8 --master-addr 127.0.0.1 tools/bench_mo.py --algo moead
 
@@ -129,7 +129,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--cpu", action="store_true")
-    ap.add_argument("--runs", type=int, default=0, help="nsga2 / gde3: this many independent seeds (one GPU)")
+    ap.add_argument("--runs", type=int, default=0, help="nsga2 / gde3 / ibea / spea2: this many independent seeds (one GPU)")
     ap.add_argument("--batched", action="store_true", help="with --runs: all seeds as one BatchedRuns workflow")
     ap.add_argument("--force-dist", action="store_true", help="sharded protocol even on one rank")
     ap.add_argument("--simulate-rank", type=int, default=None,  # -1 (MOEA/D): the rank with the largest halo
@@ -139,8 +139,8 @@ def main():
     ap.add_argument("--link-gbps", type=float, default=None, help="--simulate-rank wire model: GB/s per xGMI link and direction")
     args = ap.parse_args()
     if args.runs or args.batched:
-        if args.algo not in ("nsga2", "gde3") or args.runs < 1 or args.gpus != 1 or args.simulate_rank is not None or args.force_dist:
-            ap.error("--runs R [--batched] needs R >= 1, --algo nsga2 or gde3, and one rank")
+        if args.algo not in ("nsga2", "gde3", "ibea", "spea2") or args.runs < 1 or args.gpus != 1 or args.simulate_rank is not None or args.force_dist:
+            ap.error("--runs R [--batched] needs R >= 1, --algo nsga2, gde3, ibea or spea2, and one rank")
         return run_seeds(args, torch.device("cpu" if args.cpu else "cuda"))
     import torch.distributed as dist
     from evoxmi.parallel import init_distributed
