@@ -1401,6 +1401,72 @@ std::vector<at::Tensor> cma_paths(const at::Tensor& ps, const at::Tensor& pc, co
   return {pso, pco, so, ao, ho};
 }
 
+// cma_small.hip: one workgroup per run.  Single run: key (2,), mean (d,), sigma () or (1,), B (d, d), D (d,), population (λ, d), …;
+// R runs: every operand gains a leading R (sigma and the counters are (R,)) and so does every output.
+void cma_small_dims(int64_t d, int64_t lam, const char* who) {
+  TORCH_CHECK(d >= 1 && d <= evx_cma_small_max_d(), who, ": 1 <= d <= ", evx_cma_small_max_d());
+  TORCH_CHECK(lam >= 1 && lam <= evx_cma_small_max_lambda(), who, ": 1 <= lambda <= ", evx_cma_small_max_lambda());
+}
+
+at::Tensor cma_small_ask(const at::Tensor& key, const at::Tensor& mean, const at::Tensor& sigma, const at::Tensor& B, const at::Tensor& D,
+                         int64_t lam) {
+  const int64_t R0 = key_batch(key, "cma_small_ask");
+  const int64_t R = R0 ? R0 : 1, d = mean.size(-1);
+  for (auto* t : {&mean, &sigma, &B, &D}) { CHECK_DEV(*t); CHECK_F32(*t); CHECK_CONTIG(*t); }
+  cma_small_dims(d, lam, "cma_small_ask");
+  TORCH_CHECK(mean.dim() == (R0 ? 2 : 1) && mean.numel() == R * d && D.numel() == R * d && B.numel() == R * d * d && sigma.numel() == R &&
+                  B.size(-1) == d && D.size(-1) == d,
+              "cma_small_ask: key (2,), mean (d,), sigma (), B (d, d), D (d,), or all of them with a leading run axis");
+  c10::DeviceGuard g(key.device());
+  auto x = R0 ? at::empty({R, lam, d}, mean.options()) : at::empty({lam, d}, mean.options());
+  evx_cma_small_ask(key.data_ptr<int64_t>(), mean.data_ptr<float>(), sigma.data_ptr<float>(), B.data_ptr<float>(), D.data_ptr<float>(),
+                    x.data_ptr<float>(), (int)R, (int)lam, (int)d, cur_stream());
+  return x;
+}
+
+std::vector<at::Tensor> cma_small_tell(const at::Tensor& population, const at::Tensor& fitness, const at::Tensor& mean,
+                                       const at::Tensor& sigma, const at::Tensor& ps, const at::Tensor& pc, const at::Tensor& C,
+                                       const at::Tensor& B, const at::Tensor& D, const at::Tensor& invsqrtC, const at::Tensor& count_iter,
+                                       const at::Tensor& count_eigen, const at::Tensor& weights, std::vector<double> consts,
+                                       int64_t decomp_per_iter, const at::Tensor& eig_stats) {
+  for (auto* t : {&population, &fitness, &mean, &sigma, &ps, &pc, &C, &B, &D, &invsqrtC, &weights}) {
+    CHECK_DEV(*t); CHECK_F32(*t); CHECK_CONTIG(*t);
+  }
+  for (auto* t : {&count_iter, &count_eigen}) {
+    CHECK_DEV(*t); CHECK_CONTIG(*t);
+    TORCH_CHECK(t->scalar_type() == at::kLong, "cma_small_tell: int64 counters");
+  }
+  CHECK_DEV(eig_stats); CHECK_CONTIG(eig_stats);
+  TORCH_CHECK(eig_stats.scalar_type() == at::kDouble, "cma_small_tell: eig_stats float64");
+  TORCH_CHECK(population.dim() == 2 || population.dim() == 3, "cma_small_tell: population (lambda, d) or (R, lambda, d)");
+  const bool batched = population.dim() == 3;
+  const int64_t R = batched ? population.size(0) : 1, lam = population.size(-2), d = population.size(-1), mu = weights.numel();
+  cma_small_dims(d, lam, "cma_small_tell");
+  TORCH_CHECK(R >= 1 && R <= EVX_MAX_RUNS, "cma_small_tell: 1 <= R <= ", EVX_MAX_RUNS, " runs in one launch");
+  TORCH_CHECK(weights.dim() == 1 && mu >= 1 && mu <= lam, "cma_small_tell: weights (mu,), shared by the runs, 1 <= mu <= lambda");
+  TORCH_CHECK(consts.size() == 10, "cma_small_tell: 10 constants (those of cma_paths, then cm)");
+  TORCH_CHECK(decomp_per_iter >= 1, "cma_small_tell: decomp_per_iter >= 1");
+  TORCH_CHECK(fitness.numel() == R * lam && mean.numel() == R * d && ps.numel() == R * d && pc.numel() == R * d && D.numel() == R * d &&
+                  sigma.numel() == R && count_iter.numel() == R && count_eigen.numel() == R && C.numel() == R * d * d &&
+                  B.numel() == R * d * d && invsqrtC.numel() == R * d * d && eig_stats.numel() == R * 4 &&
+                  mean.dim() == (batched ? 2 : 1) && mean.size(-1) == d,
+              "cma_small_tell: state shapes do not match population (R, lambda, d)");
+  c10::DeviceGuard g(population.device());
+  float k[10];
+  for (int i = 0; i < 10; ++i) k[i] = (float)consts[i];
+  auto mo = at::empty_like(mean), pso = at::empty_like(ps), pco = at::empty_like(pc), so = at::empty_like(sigma), Co = at::empty_like(C);
+  auto Bo = at::empty_like(B), Do = at::empty_like(D), Io = at::empty_like(invsqrtC), ceo = at::empty_like(count_eigen);
+  auto eo = at::empty_like(eig_stats);
+  const EvxCmaSmallTell a{population.data_ptr<float>(), fitness.data_ptr<float>(), mean.data_ptr<float>(), sigma.data_ptr<float>(),
+                          ps.data_ptr<float>(), pc.data_ptr<float>(), C.data_ptr<float>(), B.data_ptr<float>(), D.data_ptr<float>(),
+                          invsqrtC.data_ptr<float>(), weights.data_ptr<float>(), count_iter.data_ptr<int64_t>(),
+                          count_eigen.data_ptr<int64_t>(), eig_stats.data_ptr<double>(), mo.data_ptr<float>(), pso.data_ptr<float>(),
+                          pco.data_ptr<float>(), so.data_ptr<float>(), Co.data_ptr<float>(), Bo.data_ptr<float>(), Do.data_ptr<float>(),
+                          Io.data_ptr<float>(), ceo.data_ptr<int64_t>(), eo.data_ptr<double>()};
+  evx_cma_small_tell(a, (int)R, (int)lam, (int)d, (int)mu, k, (int)decomp_per_iter, cur_stream());
+  return {mo, pso, pco, so, Co, Bo, Do, Io, ceo, eo};
+}
+
 std::vector<at::Tensor> cma_cov_pad(const at::Tensor& C, const at::Tensor& S, const at::Tensor& pc, const at::Tensor& a, double c1,
                                     double cmu, const at::Tensor& Bprev, int64_t np, const c10::optional<at::Tensor>& Cn_out,
                                     bool want_bp) {
@@ -2036,6 +2102,8 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("cma_local_select(Tensor order, int mu, Tensor w, int start, int size, Tensor(a!) rows, Tensor(b!) wk) -> ()");
   m.def("sym_pack(Tensor S, Tensor(a!) P) -> ()");
   m.def("sym_unpack(Tensor P, Tensor(a!) S) -> ()");
+  m.def("cma_small_ask(Tensor key, Tensor mean, Tensor sigma, Tensor B, Tensor D, int lam) -> Tensor");
+  m.def("cma_small_tell(Tensor population, Tensor fitness, Tensor mean, Tensor sigma, Tensor ps, Tensor pc, Tensor C, Tensor B, Tensor D, Tensor invsqrtC, Tensor count_iter, Tensor count_eigen, Tensor weights, float[] consts, int decomp_per_iter, Tensor eig_stats) -> Tensor[]");
   m.def("cma_paths(Tensor ps, Tensor pc, Tensor y, Tensor delta, Tensor sigma, Tensor count_iter, float[] consts, Tensor? count_eigen=None) -> Tensor[]");
   m.def("cma_cov_pad(Tensor C, Tensor S, Tensor pc, Tensor a, float c1, float cmu, Tensor Bprev, int np, Tensor? Cn_out=None, bool want_bp=True) -> Tensor[]");
   m.def("cma_eig_out(Tensor Bp, Tensor w, int d, Tensor? B_out=None, Tensor? B_alt=None, Tensor? keep=None) -> Tensor[]");
@@ -2142,6 +2210,8 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("sym_pack", &sym_pack);
   m.impl("sym_unpack", &sym_unpack);
   m.impl("cma_paths", &cma_paths);
+  m.impl("cma_small_ask", &cma_small_ask);
+  m.impl("cma_small_tell", &cma_small_tell);
   m.impl("cma_cov_pad", &cma_cov_pad);
   m.impl("cma_eig_out", &cma_eig_out);
   m.impl("nsga_select", &nsga_select);

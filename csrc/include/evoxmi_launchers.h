@@ -319,6 +319,24 @@ void evx_spea2_fitness(const float* obj, int B, int n, int m, int32_t* S, uint8_
 void evx_spea2_neighbours(const float* obj, int B, int n, int m, const uint8_t* mask, float* nn_d2, int32_t* nn_idx, hipStream_t s);
 void evx_spea2_truncate(const float* objT, int B, int n, int M, const uint8_t* mask, const float* nn_d2, const int32_t* nn_idx, int n_keep,
                         uint8_t* keep, int64_t* order, int n_order, int32_t* stats, hipStream_t s);
+// cma_small.hip: a CMA-ES generation of R independent runs in two launches, one workgroup per run (d ≤ evx_cma_small_max_d(),
+// μ ≤ λ ≤ evx_cma_small_max_lambda()).  Every array has a leading run axis; the weights (μ) and the constants are shared.
+// ask: x (R, λ, d) = mean + σ·(B∘D)·z with z the run's normal stream (philox_fill(key, λ·d, 1, 0)).
+// tell: the whole of CMAES.tell; consts = the nine of evx_cma_paths, then cm; eig_stats rows = [off_rel, sweeps, 0, capped], carried
+// over by a generation that does not decompose (count_iter % decomp_per_iter != 0).
+int evx_cma_small_max_d();
+int evx_cma_small_max_lambda();
+void evx_cma_small_ask(const int64_t* key, const float* mean, const float* sigma, const float* B, const float* D, float* x, int R, int lam,
+                       int d, hipStream_t s);
+struct EvxCmaSmallTell {
+  const float *population, *fitness, *mean, *sigma, *ps, *pc, *C, *B, *D, *invsqrtC, *weights;
+  const int64_t *count_iter, *count_eigen;
+  const double* eig_stats;
+  float *mean_out, *ps_out, *pc_out, *sigma_out, *C_out, *B_out, *D_out, *invsqrtC_out;
+  int64_t* count_eigen_out;
+  double* eig_stats_out;
+};
+void evx_cma_small_tell(const EvxCmaSmallTell& a, int R, int lam, int d, int mu, const float* consts, int decomp_per_iter, hipStream_t s);
 // bce_select.hip: BCE-IBEA's PC selection and exploration (objT the (M, n) transpose zero padded to M = evx_padded_m(m) rows;
 // ws evx_bce_ws_floats() floats: the spans and, last, the niche radius; cnt one word, the rows of the mask).  evx_bce_mask: the rows no
 // row dominates; evx_bce_niche: spans, t (n,) and the radius over the masked rows (mask == nullptr: all; with n_keep ≥ 0 t and the radius

@@ -29,6 +29,11 @@ units (merged populations of at most 8192 rows and 16 objectives per run; above 
 ``NotImplementedError``).  SPEA2's runs each count their own removals.  On the CPU SPEA2's fitness and selection
 run run by run inside Python-registered ops (``evoxmi.ops.spea2``); IBEA's torch path is traced by ``vmap`` itself.
 
+CMA-ES batches on a HIP device through ``CMAES(..., fused_small=True)`` (d ≤ 64, λ ≤ 1024; ``tests/test_cma_small_gpu.py``): its
+ask and tell are two ops with one workgroup per run (``cma_small.hip``), so R seeds advance with the launches of one and run r is
+bit-identical to the flagged algorithm alone.  ``BatchedRuns(CMAES)`` without the flag works on the CPU only: on a device its
+tell goes through ops without a vmap rule.
+
 Covered multi-objective algorithms: NSGA-II, GDE3, IBEA, SPEA2.  The others are not, and an uncovered one is not
 guaranteed to raise.  Most raise from ``vmap`` (their selections read the host or loop on data), but RVEA runs and its
 runs differ from solo runs: do not rely on ``BatchedRuns`` over an algorithm that is not listed here.

@@ -24,6 +24,17 @@ synchronisation, hipGraph-capturable):
   (Philox counters are global row indices, so 1/2/4/8 GPUs sample the same
   population), fitness is all-gathered, and each rank all-reduces its partial
   weighted sums (d + d² floats) over RCCL; the state stays replicated.
+
+At benchmark dimensions (CEC 2022: d = 10, 20, λ = 10–12) that machinery is tens of launches for a
+20 × 20 matrix.  ``CMAES(..., fused_small=True)`` (d ≤ 64, λ ≤ 1024) runs a generation on a HIP device as
+about four launches: the key split, ``cma_small_ask`` (sampling, one workgroup per 32 rows), the
+``count_iter`` increment and ``cma_small_tell`` — one workgroup that ranks the fitness, updates mean, paths,
+σ and C, and re-diagonalises C by warm-started cyclic Jacobi in LDS (``csrc/kernels/cma_small.hip``).  Both
+ops take a leading run axis, so ``BatchedRuns(CMAES(..., fused_small=True), R)`` advances R seeds with the
+same launches, one workgroup per run.  The flag's trajectory is its own: its eigensolver leaves the
+eigenvectors in the order and with the signs the warm start carries, so its samples differ from those of
+``fused_small=False`` from the first non-trivial decomposition on (both are CMA-ES; they are not comparable
+sample by sample).  On CPU tensors the flag is accepted and the torch path runs unchanged.
 """
 from __future__ import annotations
 
@@ -53,8 +64,9 @@ class CMAES(Algorithm):
     # fields that differ across ranks under the sharded protocol (excluded from replica checks)
     rank_local_fields = ("population",)
 
-    def __init__(self, center_init, init_stdev, pop_size=None, recombination_weights=None, cm=1, eig_sweeps=None):
+    def __init__(self, center_init, init_stdev, pop_size=None, recombination_weights=None, cm=1, eig_sweeps=None, fused_small=False):
         super().__init__()
+        self.fused_small = bool(fused_small)
         self.center_init = center_init
         assert init_stdev > 0, "Expect variance to be a non-negative float"
         self.init_stdev = float(init_stdev)
@@ -75,6 +87,12 @@ class CMAES(Algorithm):
             self.weights = rw
         self.weights = self.weights.to(center_init.device)
         self._set_rates()
+        if self.fused_small:
+            from ....ops import cma_small
+
+            if not cma_small.caps_ok(self.dim, self.pop_size):
+                raise ValueError(f"CMAES(fused_small=True) needs 1 <= d <= {cma_small.D_CAP} and pop_size <= {cma_small.LAMBDA_CAP}, "
+                                 f"got d = {self.dim}, pop_size = {self.pop_size}")
         # iteration plans of the converged eigensolver, private to this optimiser run
         # (evoxmi.ops.sbr.eigh_warm): results depend only on the run's own history
         self._eig_plans = {}
@@ -117,7 +135,7 @@ class CMAES(Algorithm):
 
     # ------------------------------------------------------------------ step variants
     def _device_eigh(self) -> bool:
-        return (self.center_init.is_cuda and self.decomp_per_iter == 1 and config.get("cma_fused") and config.get("eigh") == "sbr"
+        return (not self._small() and self.center_init.is_cuda and self.decomp_per_iter == 1 and config.get("cma_fused") and config.get("eigh") == "sbr"
                 and config.get("sbr_mode") == "device" and self.dim % 4 == 0 and self.dim <= 8192)
 
     # ------------------------------------------------------------------ eigensolver schedule
@@ -190,7 +208,7 @@ class CMAES(Algorithm):
         return self.LEVELS
 
     def after_step(self, generation: int) -> None:
-        if self.__dict__.get("_eig_ring") is None or not torch.cuda.is_available():
+        if self._small() or self.__dict__.get("_eig_ring") is None or not torch.cuda.is_available():
             return
         sc = self._sched()
         ev = torch.cuda.Event()
@@ -315,7 +333,36 @@ class CMAES(Algorithm):
     def _advance(self, state):
         return state if self._counts_in_tell(state) else state.update(count_iter=state.count_iter + 1)
 
+    # ------------------------------------------------------------------ one-workgroup generation (fused_small)
+    def _small(self) -> bool:
+        return self.fused_small and self.center_init.is_cuda
+
+    def _small_ask(self, state):
+        from ....ops import _ext
+
+        key, sample_key = rnd.split(state.key)
+        population = _ext.ops().cma_small_ask(sample_key.contiguous(), state.mean.contiguous(), state.sigma.contiguous(),
+                                              state.B.contiguous(), state.D.contiguous(), self.pop_size)
+        return population, state.update(population=population, key=key, count_iter=state.count_iter + 1)
+
+    def _small_tell(self, state, fitness):
+        from ....ops import _ext
+
+        d = self.dim
+        consts = [self.cs, math.sqrt(self.cs * (2 - self.cs) * self.mueff), self.cc, math.sqrt(self.cc * (2 - self.cc) * self.mueff),
+                  self.chiN, self.damps, self.c1, self.cmu, (1.4 + 2 / (d + 1)) * self.chiN, float(self.cm)]
+        f = fitness.to(torch.float32).contiguous()
+        mean, ps, pc, sigma, C, B, D, invsqrtC, count_eigen, eig_stats = _ext.ops().cma_small_tell(
+            state.population.contiguous(), f, state.mean.contiguous(), state.sigma.contiguous(), state.ps.contiguous(),
+            state.pc.contiguous(), state.C.contiguous(), state.B.contiguous(), state.D.contiguous(), state.invsqrtC.contiguous(),
+            state.count_iter.contiguous(), state.count_eigen.contiguous(), self.weights, consts, self.decomp_per_iter,
+            state.eig_stats.contiguous())
+        return state.update(mean=mean, ps=ps, pc=pc, sigma=sigma, C=C, B=B, D=D, invsqrtC=invsqrtC, count_eigen=count_eigen,
+                            eig_stats=eig_stats)
+
     def ask(self, state):
+        if self._small():
+            return self._small_ask(state)
         key, sample_key = rnd.split(state.key)
         population = self._sample(state, sample_key, 0, self.pop_size)
         return population, self._advance(state).update(population=population, key=key)
@@ -494,6 +541,8 @@ class CMAES(Algorithm):
         return B, D, invsqrtC
 
     def tell(self, state, fitness):
+        if self._small():
+            return self._small_tell(state, fitness)
         pop = state.population
         if self._aug_ok(pop):
             _, order = argsort_i32(fitness.contiguous())
@@ -510,6 +559,8 @@ class CMAES(Algorithm):
 
     # ------------------------------------------------------------------ SPMD protocol
     def ask_sharded(self, state, dist):
+        if self.fused_small:
+            raise NotImplementedError("CMAES(fused_small=True) has no sharded protocol")
         start, size = dist.slice_of(self.pop_size)
         key, sample_key = rnd.split(state.key)
         local = self._sample(state, sample_key, start, size)
@@ -525,6 +576,8 @@ class CMAES(Algorithm):
         the weighted mean shift appended: d(d+1)/2 + d floats, half the bytes of round 5's
         (d² + d) all-reduce.  Reference: ``cma_es.py:163-198`` (tell), whose ``Σ wᵢ yᵢ yᵢᵀ`` is
         this sum over ranks."""
+        if self.fused_small:
+            raise NotImplementedError("CMAES(fused_small=True) has no sharded protocol")
         start, size = dist.slice_of(self.pop_size)
         d = self.dim
         K = min(self.mu, size)

@@ -18,7 +18,9 @@ per run).  Each rule moves the run axis to the front and calls the op's batched 
 * ``ibea_fitness`` / ``spea2_fitness``: obj (B, n, m) → grid.y = run (``ibea_select.hip``, ``spea2_select.hip``; m ≤ 16, for
   SPEA2 n ≤ 32768 per run);
 * ``ibea_truncate`` / ``spea2_truncate``: obj (B, n, m), per-row operands (B, n) → one workgroup per run, whose removal loop
-  is the single-run one (n ≤ 8192, m ≤ 16 per run); SPEA2's runs each count their own removals.
+  is the single-run one (n ≤ 8192, m ≤ 16 per run); SPEA2's runs each count their own removals;
+* ``cma_small_ask`` / ``cma_small_tell``: every state field (B, …) → one workgroup per run (``cma_small.hip``; d ≤ 64, λ ≤ 1024
+  per run), the recombination weights and the constants shared by the runs.
 
 Each run's words/trials are bit-identical to the single-run op with that run's key
 (``tests/test_batched_runs.py``), each run's sorted keys and indices to the op applied row by row
@@ -170,6 +172,31 @@ def _spea2_truncate(info, in_dims, obj, mask, n_keep, nn_d2=None, nn_idx=None):
     return list(_ext.ops().spea2_truncate(ob, _runs_of(mask, in_dims[1], B, 1, what), n_keep, nn_d2, nn_idx)), [0, 0, 0]
 
 
+def _cma_small_ask(info, in_dims, key, mean, sigma, B, D, lam):
+    from .cma_small import check_batched_caps
+
+    R, what = info.batch_size, "cma_small_ask vmap rule"
+    mb = _runs_of(mean, in_dims[1], R, 1, what)
+    check_batched_caps(mb.shape[1], lam, what)
+    return _ext.ops().cma_small_ask(_runs_of(key, in_dims[0], R, 1, what), mb, _runs_of(sigma, in_dims[2], R, 0, what),
+                                    _runs_of(B, in_dims[3], R, 2, what), _runs_of(D, in_dims[4], R, 1, what), lam), 0
+
+
+def _cma_small_tell(info, in_dims, population, fitness, mean, sigma, ps, pc, C, B, D, invsqrtC, count_iter, count_eigen, weights, consts,
+                    decomp_per_iter, eig_stats):
+    from .cma_small import check_batched_caps
+
+    R, what = info.batch_size, "cma_small_tell vmap rule"
+    if in_dims[12] is not None:
+        raise NotImplementedError(f"{what}: the recombination weights must be shared by all runs")
+    pb = _runs_of(population, in_dims[0], R, 2, what)
+    check_batched_caps(pb.shape[2], pb.shape[1], what)
+    per_run = ((fitness, 1), (mean, 1), (sigma, 0), (ps, 1), (pc, 1), (C, 2), (B, 2), (D, 1), (invsqrtC, 2), (count_iter, 0), (count_eigen, 0))
+    args = [_runs_of(t, bd, R, nd, what) for (t, nd), bd in zip(per_run, in_dims[1:12])]
+    out = _ext.ops().cma_small_tell(pb, *args, weights, consts, decomp_per_iter, _runs_of(eig_stats, in_dims[15], R, 1, what))
+    return list(out), [0] * 10
+
+
 def register():
     """Install the rules (idempotent).  Without the compiled extension there is nothing to
     batch: CPU tensors never reach the HIP ops, and a device op raises on its own."""
@@ -179,6 +206,6 @@ def register():
     for name, fn in (("philox_words", _philox_words), ("philox_fill", _philox_fill), ("rank_argsort_f32", _rank_argsort_f32),
                      ("de_trial", _de_trial), ("sbx", _sbx), ("pm", _pm), ("nds", _nds), ("nsga_select", _nsga_select),
                      ("ibea_fitness", _ibea_fitness), ("ibea_truncate", _ibea_truncate), ("spea2_fitness", _spea2_fitness),
-                     ("spea2_truncate", _spea2_truncate)):
+                     ("spea2_truncate", _spea2_truncate), ("cma_small_ask", _cma_small_ask), ("cma_small_tell", _cma_small_tell)):
         torch.library.register_vmap(f"evoxmi::{name}", fn)
     _REGISTERED = True

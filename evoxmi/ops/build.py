@@ -89,7 +89,10 @@ def _run(cmd):
 # hv_exact.hip: its accuracy contract counts one rounding per float64 operation of the stated formulas, so none may fuse
 # planar_rollout.hip: its sub-step is scalar f32 arithmetic; SLP packing adds ~190 v_mov per
 # sub-step (835 instructions against 704 without it in the two-chain instantiation)
-FILE_FLAGS = {"eigh_sbr.hip": ["-fno-slp-vectorize"], "mo_geom.hip": ["-ffp-contract=fast-honor-pragmas"],
+# cma_small.hip: its ask draws the normals of rng.hip bit for bit, so it takes that file's contraction mode (plain "fast" also fuses
+# inside the inlined logf / sincosf); packed f32 arithmetic is off for this file: nothing in it is written for v_pk_* issue
+FILE_FLAGS = {"cma_small.hip": ["-ffp-contract=fast-honor-pragmas", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              "eigh_sbr.hip": ["-fno-slp-vectorize"], "mo_geom.hip": ["-ffp-contract=fast-honor-pragmas"],
               "knea_select.hip": ["-ffp-contract=off"], "rvea_select.hip": ["-ffp-contract=off"],
               "bige_select.hip": ["-ffp-contract=off"], "tdea_select.hip": ["-ffp-contract=off"],
               "hv_exact.hip": ["-ffp-contract=off"], "rng.hip": ["-ffp-contract=fast-honor-pragmas"],
