@@ -1287,6 +1287,86 @@ void moead_select_rows_(at::Tensor& pop, const at::Tensor& off, const at::Tensor
                                   cur_stream());
 }
 
+// ---- moead_small.hip: R runs per launch.  A single run passes pop (N, d), nb (N, T), key (2,), kx / km (2, 2), objectives and W (N, m),
+// z (m,); R runs give every operand a leading R, except lb / ub (shared) and nb / W, whose leading axis may be 1 (shared).
+bool rows_aligned16(std::initializer_list<const at::Tensor*> ts) {
+  for (auto* t : ts)
+    if (reinterpret_cast<uintptr_t>(t->data_ptr()) & 15) return false;
+  return true;
+}
+
+// the leading axis of an operand that may be shared by the runs: 1 where it is per run, 0 where shared
+int run_axis(const at::Tensor& t, int64_t per_run_dim, bool batched, int64_t R, const char* who, const char* name) {
+  if (!batched) {
+    TORCH_CHECK(t.dim() == per_run_dim, who, ": ", name, " must have ", per_run_dim, " dimensions next to a single run");
+    return 0;
+  }
+  TORCH_CHECK(t.dim() == per_run_dim + 1 && (t.size(0) == R || t.size(0) == 1), who, ": ", name, " must lead with the run axis (R or 1)");
+  return t.size(0) == R && R > 1 ? 1 : 0;
+}
+
+std::vector<at::Tensor> moead_small_ask(const at::Tensor& pop, const at::Tensor& nb, const at::Tensor& key, const at::Tensor& kx,
+                                        const at::Tensor& km, const at::Tensor& lb, const at::Tensor& ub, double pro_c, double dis_c,
+                                        double pro_m, double dis_m, int64_t nm) {
+  const char* who = "moead_small_ask";
+  for (auto* t : {&pop, &lb, &ub}) { CHECK_DEV(*t); CHECK_F32(*t); CHECK_CONTIG(*t); }
+  CHECK_DEV(nb); CHECK_CONTIG(nb);
+  TORCH_CHECK(nb.scalar_type() == at::kLong, who, ": neighbours must be int64");
+  TORCH_CHECK(pop.dim() == 2 || pop.dim() == 3, who, ": pop (N, d) or (R, N, d)");
+  const bool batched = pop.dim() == 3;
+  const int64_t R = batched ? pop.size(0) : 1, N = pop.size(-2), d = pop.size(-1), T = nb.size(-1);
+  const int64_t R0 = key_batch(key, who);
+  TORCH_CHECK(batched ? R0 == R : R0 == 0, who, ": key (2,) for a single run, (R, 2) for R runs");
+  TORCH_CHECK(R >= 1 && R <= EVX_MAX_RUNS, who, ": 1 <= R <= ", EVX_MAX_RUNS, " runs in one launch");
+  for (auto* t : {&kx, &km})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kLong && t->is_contiguous() && t->numel() == R * 4 && t->dim() == (batched ? 3 : 2),
+                who, ": kx and km must be int64 (2, 2) per run on device");
+  const int nb_per_run = run_axis(nb, 2, batched, R, who, "neighbours");
+  TORCH_CHECK(N >= 1 && d >= 1 && nb.size(-2) == N && T >= 1 && T < 65536, who, ": neighbours must be (N, T), 1 <= T < 65536, N, d >= 1");
+  TORCH_CHECK(lb.numel() == d && ub.numel() == d, who, ": bounds must be (d,), shared by the runs");
+  TORCH_CHECK(nm >= 0 && nm <= N, who, ": 0 <= nm <= N");
+  TORCH_CHECK((N + 3) / 4 <= 2147483647 && N * T <= 2147483647 && N * d <= 2147483647, who, ": N·T and N·d must fit 31 bits");
+  c10::DeviceGuard g(pop.device());
+  auto off = at::empty_like(pop);
+  auto parents = batched ? at::empty({R, 2, N}, pop.options().dtype(at::kInt)) : at::empty({2, N}, pop.options().dtype(at::kInt));
+  evx_moead_small_ask(pop.data_ptr<float>(), nb.data_ptr<int64_t>(), nb_per_run, key.data_ptr<int64_t>(), kx.data_ptr<int64_t>(),
+                      km.data_ptr<int64_t>(), lb.data_ptr<float>(), ub.data_ptr<float>(), (float)pro_c, (float)dis_c, (float)pro_m,
+                      (float)dis_m, (int)nm, (int)R, (int)N, (int)T, (int)d, rows_aligned16({&pop, &off, &lb, &ub}), off.data_ptr<float>(),
+                      parents.data_ptr<int>(), cur_stream());
+  return {off, parents};
+}
+
+std::vector<at::Tensor> moead_small_tell(const at::Tensor& pop, const at::Tensor& off, const at::Tensor& pop_obj, const at::Tensor& off_obj,
+                                         const at::Tensor& W, const at::Tensor& nb, const at::Tensor& z, int64_t func) {
+  const char* who = "moead_small_tell";
+  for (auto* t : {&pop, &off, &pop_obj, &off_obj, &W, &z}) { CHECK_DEV(*t); CHECK_F32(*t); CHECK_CONTIG(*t); }
+  CHECK_DEV(nb); CHECK_CONTIG(nb);
+  TORCH_CHECK(nb.scalar_type() == at::kLong, who, ": neighbours must be int64");
+  TORCH_CHECK(pop.dim() == 2 || pop.dim() == 3, who, ": pop (N, d) or (R, N, d)");
+  const bool batched = pop.dim() == 3;
+  const int64_t R = batched ? pop.size(0) : 1, N = pop.size(-2), d = pop.size(-1), M = pop_obj.size(-1), T = nb.size(-1);
+  TORCH_CHECK(R >= 1 && R <= EVX_MAX_RUNS, who, ": 1 <= R <= ", EVX_MAX_RUNS, " runs in one launch");
+  TORCH_CHECK(N >= 1 && N <= evx_moead_small_max_n(), who, ": 1 <= N <= ", evx_moead_small_max_n(), " slots per run, got ", N);
+  TORCH_CHECK(M >= 1 && M <= evx_moead_small_max_m(), who, ": 1 <= m <= ", evx_moead_small_max_m(), " objectives, got ", M);
+  TORCH_CHECK(d >= 1 && off.sizes() == pop.sizes(), who, ": off must have the shape of pop, d >= 1");
+  TORCH_CHECK(pop_obj.dim() == pop.dim() && pop_obj.numel() == R * N * M && pop_obj.size(-2) == N && off_obj.sizes() == pop_obj.sizes(),
+              who, ": pop_obj and off_obj must be (N, m) per run");
+  TORCH_CHECK(z.numel() == R * M && z.dim() == (batched ? 2 : 1), who, ": z must be (m,) per run");
+  const int w_per_run = run_axis(W, 2, batched, R, who, "W"), nb_per_run = run_axis(nb, 2, batched, R, who, "neighbours");
+  TORCH_CHECK(W.size(-2) == N && W.size(-1) == M, who, ": W must be (N, m)");
+  TORCH_CHECK(nb.size(-2) == N && T >= 1 && T <= N, who, ": neighbours must be (N, T), 1 <= T <= N");
+  TORCH_CHECK(func >= 0 && func <= 4, who, ": func 0..4");
+  TORCH_CHECK(N * d <= 2147483647, who, ": N·d must fit 31 bits");
+  c10::DeviceGuard g(pop.device());
+  auto new_pop = at::empty_like(pop), new_obj = at::empty_like(pop_obj), zo = at::empty_like(z);
+  auto win = batched ? at::empty({R, N}, pop.options().dtype(at::kInt)) : at::empty({N}, pop.options().dtype(at::kInt));
+  evx_moead_small_tell(pop.data_ptr<float>(), off.data_ptr<float>(), pop_obj.data_ptr<float>(), off_obj.data_ptr<float>(), W.data_ptr<float>(),
+                       w_per_run, nb.data_ptr<int64_t>(), nb_per_run, z.data_ptr<float>(), (int)func, (int)R, (int)N, (int)T, (int)M, (int)d,
+                       rows_aligned16({&pop, &off, &new_pop}), new_pop.data_ptr<float>(), new_obj.data_ptr<float>(), zo.data_ptr<float>(),
+                       win.data_ptr<int>(), cur_stream());
+  return {new_pop, new_obj, zo, win};
+}
+
 at::Tensor lsmop_g(const at::Tensor& X, std::vector<int64_t> start, std::vector<int64_t> sublen, std::vector<int64_t> func, int64_t nk, int64_t cosine) {
   CHECK_DEV(X); CHECK_F32(X); CHECK_CONTIG(X);
   const int64_t ng = (int64_t)start.size();
@@ -2138,6 +2218,8 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("moead_replace(Tensor pop_obj, Tensor off_obj, Tensor W, Tensor z, Tensor zmax, Tensor rowptr, Tensor owner, int func) -> Tensor[]");
   m.def("moead_select_rows(Tensor pop, Tensor off, Tensor win) -> Tensor");
   m.def("moead_select_rows_(Tensor(a!) pop, Tensor off, Tensor win) -> ()");
+  m.def("moead_small_ask(Tensor pop, Tensor nb, Tensor key, Tensor kx, Tensor km, Tensor lb, Tensor ub, float pro_c, float dis_c, float pro_m, float dis_m, int nm) -> Tensor[]");
+  m.def("moead_small_tell(Tensor pop, Tensor off, Tensor pop_obj, Tensor off_obj, Tensor W, Tensor nb, Tensor z, int func) -> Tensor[]");
   m.def("sbr_stats(Tensor A) -> Tensor");
   m.def("sbr_symstats(Tensor T) -> Tensor[]");
   m.def("sbr16_block(Tensor A, int shift, int sweeps, int sb=16) -> Tensor[]");
@@ -2238,6 +2320,8 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("moead_replace", &moead_replace);
   m.impl("moead_select_rows_", &moead_select_rows_);
   m.impl("moead_select_rows", &moead_select_rows);
+  m.impl("moead_small_ask", &moead_small_ask);
+  m.impl("moead_small_tell", &moead_small_tell);
   m.impl("sbr_stats", &sbr_stats);
   m.impl("es_noise_grad", &es_noise_grad);
   m.impl("es_population", &es_population);

@@ -337,6 +337,21 @@ struct EvxCmaSmallTell {
   double* eig_stats_out;
 };
 void evx_cma_small_tell(const EvxCmaSmallTell& a, int R, int lam, int d, int mu, const float* consts, int decomp_per_iter, hipStream_t s);
+// moead_small.hip: a MOEA/D generation of R independent runs in two launches.  Every array has a leading run axis except lb / ub
+// (shared) and, where nb_per_run / w_per_run is 0, the neighbour table (N, T) and the weights (N, M).  vec4: every row of pop, off,
+// lb, ub and the outputs is 16-byte aligned (float4 accesses where d % 4 == 0).
+// ask: a wave per offspring; off (R, N, d) and parents (R, 2, N) = moead_parents + moead_variation of every run (key (R, 2),
+// kx / km (R, 2, 2) the split variation keys).
+// tell: one workgroup per run (N ≤ evx_moead_small_max_n(), M ≤ evx_moead_small_max_m(), T ≤ N); z' = min(z, colmin(off_obj)),
+// z_max = colmax(pop_obj), then win (R, N), new_obj and new_pop = moead_replace + moead_select_rows of every run, without a CSR.
+int evx_moead_small_max_n();
+int evx_moead_small_max_m();
+void evx_moead_small_ask(const float* pop, const int64_t* nb, int nb_per_run, const int64_t* key, const int64_t* kx, const int64_t* km,
+                         const float* lb, const float* ub, float pro_c, float dis_c, float pro_m, float dis_m, int nm, int R, int N, int T,
+                         int d, bool vec4, float* off, int32_t* parents, hipStream_t s);
+void evx_moead_small_tell(const float* pop, const float* off, const float* pop_obj, const float* off_obj, const float* W, int w_per_run,
+                          const int64_t* nb, int nb_per_run, const float* z, int func, int R, int N, int T, int M, int d, bool vec4,
+                          float* new_pop, float* new_obj, float* zout, int32_t* win, hipStream_t s);
 // bce_select.hip: BCE-IBEA's PC selection and exploration (objT the (M, n) transpose zero padded to M = evx_padded_m(m) rows;
 // ws evx_bce_ws_floats() floats: the spans and, last, the niche radius; cnt one word, the rows of the mask).  evx_bce_mask: the rows no
 // row dominates; evx_bce_niche: spans, t (n,) and the radius over the masked rows (mask == nullptr: all; with n_keep ≥ 0 t and the radius

@@ -34,7 +34,13 @@ ask and tell are two ops with one workgroup per run (``cma_small.hip``), so R se
 bit-identical to the flagged algorithm alone.  ``BatchedRuns(CMAES)`` without the flag works on the CPU only: on a device its
 tell goes through ops without a vmap rule.
 
-Covered multi-objective algorithms: NSGA-II, GDE3, IBEA, SPEA2.  The others are not, and an uncovered one is not
+MOEA/D batches as well (``tests/test_batched_moead.py``, ``tests/test_batched_moead_gpu.py``): on a HIP device a generation is the two
+launches of ``moead_small.hip`` — a wave per offspring draws its parents and varies its genes; one workgroup per run forms the
+reference points, replaces without a reverse-neighbour CSR and selects the rows — for the default SBX(type 2) + polynomial-mutation
+pipeline, float32 and at most 2048 subproblems and 16 objectives per run (``NotImplementedError`` otherwise); on the CPU its tell runs
+run by run inside a Python-registered op.  ``MOEADDRA``, ``EAGMOEAD`` and ``MOEADM2M`` are not covered.
+
+Covered multi-objective algorithms: NSGA-II, GDE3, IBEA, SPEA2, MOEA/D.  The others are not, and an uncovered one is not
 guaranteed to raise.  Most raise from ``vmap`` (their selections read the host or loop on data), but RVEA runs and its
 runs differ from solo runs: do not rely on ``BatchedRuns`` over an algorithm that is not listed here.
 """

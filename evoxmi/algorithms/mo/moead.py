@@ -16,10 +16,19 @@ reduces per slot (a segmented first-argmin over the reverse-neighbour CSR),
 then gathers only the winning rows.  At N = 16384, d = 10 000 this replaces
 16 384 dependent steps (each moving T rows of 10 000 floats) with one parallel
 pass plus one row gather.
+
+``BatchedRuns(MOEAD(...), R)`` — R seeds as one computation.  Under ``vmap`` ``ask`` and ``tell`` take a branch of their own
+before any pointer, capture or cache logic: on a HIP device the two launches of ``moead_small.hip`` (a wave per offspring
+for parents and variation; one workgroup per run for the reference points, the replacement without a reverse-neighbour
+CSR and the row selection), which need the default SBX(type 2) + polynomial-mutation pipeline, float32 and at most 2048
+slots and 16 objectives per run (``NotImplementedError`` otherwise); on the CPU the torch path for ``ask`` and a
+Python-registered op for ``tell`` that runs ``moead_replace`` and the row selection run by run.  Run r is bit-identical to
+the algorithm alone from ``split(key, R)[r]``.  ``MOEADDRA``, ``EAGMOEAD`` and ``MOEADM2M`` are not covered.
 """
 from __future__ import annotations
 
 import math
+from typing import Tuple
 
 import torch
 
@@ -28,6 +37,7 @@ from ...operators import crossover, mutation
 from ...operators.sampling import UniformSampling
 from ...ops import geom
 from ...ops import random as rnd
+from ...ops.nds import _in_vmap
 from ...utils.common import AggregationFunction
 
 
@@ -81,6 +91,47 @@ def moead_replace(pop_obj, off_obj, w, z, z_max, agg, rev):
     win = torch.where(better & has, rev_owner[first.clamp_max(f_new.shape[0] - 1)], torch.full_like(first, -1))
     new_obj = torch.where((win >= 0)[:, None], off_obj[win.clamp_min(0)], pop_obj)
     return win, new_obj
+
+
+def _tell_torch(pop, off, pop_obj, off_obj, w, neighbors, z, func: str):
+    """One run of the torch ``tell``: (new_pop, new_obj, z', win int32), the operations of ``MOEAD._replace`` and ``tell``."""
+    z = torch.minimum(z, off_obj.min(0).values)
+    z_max = pop_obj.max(0).values
+    win, new_obj = moead_replace(pop_obj, off_obj, w, z, z_max, AggregationFunction(func), reverse_neighbors(neighbors))
+    win = win.to(torch.int32)
+    return torch.where((win >= 0)[:, None], off[win.long().clamp_min(0)], pop), new_obj, z, win
+
+
+# What a vmapped ``tell`` reaches on the CPU: ``vmap`` cannot trace ``reverse_neighbors`` (in-place writes, sorts whose sizes
+# depend on data), so ``_tell_run`` is one run as an op and its rule is ``_tell_runs``, the same function run by run: by
+# construction the sequential result (as ``evoxmi.ops.spea2`` does for its CPU runs).
+@torch.library.custom_op("evoxmi_py::moead_tell_runs", mutates_args=())
+def _tell_runs(pop: torch.Tensor, off: torch.Tensor, pop_obj: torch.Tensor, off_obj: torch.Tensor, w: torch.Tensor, neighbors: torch.Tensor,
+               z: torch.Tensor, func: str) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return tuple(torch.stack(t) for t in zip(*[_tell_torch(*a, func) for a in zip(pop, off, pop_obj, off_obj, w, neighbors, z)]))
+
+
+@_tell_runs.register_fake
+def _(pop, off, pop_obj, off_obj, w, neighbors, z, func):
+    return torch.empty_like(pop), torch.empty_like(pop_obj), torch.empty_like(z), pop.new_empty(pop.shape[:2], dtype=torch.int32)
+
+
+@torch.library.custom_op("evoxmi_py::moead_tell_run", mutates_args=())
+def _tell_run(pop: torch.Tensor, off: torch.Tensor, pop_obj: torch.Tensor, off_obj: torch.Tensor, w: torch.Tensor, neighbors: torch.Tensor,
+              z: torch.Tensor, func: str) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _tell_torch(pop, off, pop_obj, off_obj, w, neighbors, z, func)
+
+
+@_tell_run.register_fake
+def _(pop, off, pop_obj, off_obj, w, neighbors, z, func):
+    return torch.empty_like(pop), torch.empty_like(pop_obj), torch.empty_like(z), pop.new_empty(pop.shape[:1], dtype=torch.int32)
+
+
+@torch.library.register_vmap("evoxmi_py::moead_tell_run")
+def _(info, in_dims, pop, off, pop_obj, off_obj, w, neighbors, z, func):
+    B = info.batch_size
+    first = lambda x, bdim: x.unsqueeze(0).expand((B,) + tuple(x.shape)) if bdim is None else x.movedim(bdim, 0)  # noqa: E731
+    return _tell_runs(*(first(x, bd) for x, bd in zip((pop, off, pop_obj, off_obj, w, neighbors, z), in_dims[:7])), func), (0, 0, 0, 0)
 
 
 def locality_order(w: torch.Tensor, leaves: int = 64) -> torch.Tensor:
@@ -164,12 +215,43 @@ class MOEAD(Algorithm):
         perm = torch.argsort(rnd.uniform(key, (n, T)).to(state.neighbors.device), dim=1, stable=True)[:, :2]
         return torch.gather(state.neighbors, 1, perm)
 
+    def _default_pipeline(self):
+        """SBX(type 2) + polynomial mutation over this algorithm's bounds: what the fused kernels compute."""
+        c, m = self.crossover, self.mutation
+        return (type(c) is crossover.SimulatedBinary and c.type == 2
+                and type(m) is mutation.Polynomial and m.boundary[0] is self.lb and m.boundary[1] is self.ub)
+
     def _fused(self, x):
         """The default SBX(type 2) + PM pipeline runs as the fused moead.hip kernels on a GPU."""
+        return x.is_cuda and x.dtype == torch.float32 and self.dim > 0 and self._default_pipeline()
+
+    # ------------------------------------------------------------------ BatchedRuns (the state tensors are inside vmap)
+    def _ask_runs(self, state):
+        """``ask`` under ``vmap`` on a device: parents and variation of every run in one launch."""
+        from ...ops import mo as mo_ops
+
+        pop = state.population
+        if not (self._default_pipeline() and pop.dtype == torch.float32 and self.dim > 0):
+            raise NotImplementedError("MOEAD under BatchedRuns on a device needs float32 and the default SBX(type 2) + Polynomial operators")
+        key, sub, sel_key, mut_key = rnd.split(state.key, 4)
         c, m = self.crossover, self.mutation
-        return (x.is_cuda and x.dtype == torch.float32 and self.dim > 0
-                and type(c) is crossover.SimulatedBinary and c.type == 2
-                and type(m) is mutation.Polynomial and m.boundary[0] is self.lb and m.boundary[1] is self.ub)
+        off, parents = mo_ops.moead_small_ask(pop, state.neighbors, sub, sel_key, mut_key, self.lb, self.ub, c.pro_c, c.dis_c, m.pro_m, m.dis_m)
+        return off, state.update(next_generation=off, key=key, parents=parents, var_keys=torch.stack([sel_key, mut_key]))
+
+    def _tell_runs(self, state, fitness):
+        """``tell`` under ``vmap``: one workgroup per run on a device, the torch path run by run on the CPU."""
+        pop = state.population
+        args = (pop, state.next_generation, state.fitness, fitness, state.weight_vector, state.neighbors, state.z)
+        if pop.is_cuda:
+            from ...ops import mo as mo_ops
+
+            if pop.dtype != torch.float32:
+                raise NotImplementedError("MOEAD under BatchedRuns on a device needs a float32 population")
+            mo_ops.check_small_caps(pop.shape[0], fitness.shape[-1], "MOEAD under BatchedRuns")
+            new_pop, new_obj, z, win = mo_ops.moead_small_tell(*args, self.func_name)
+        else:
+            new_pop, new_obj, z, win = _tell_run(*args, self.func_name)
+        return state.update(population=new_pop, fitness=new_obj, z=z, win=win)
 
     def _parent_pairs(self, state, key, row0=0, rows=0):
         """(2, N) int32: the two parents of every offspring (first two entries of a random
@@ -200,6 +282,8 @@ class MOEAD(Algorithm):
         return off[row0 : row0 + rows] if rows else off
 
     def ask(self, state):
+        if _in_vmap(state.population) and state.population.is_cuda:
+            return self._ask_runs(state)  # on the CPU the torch path below is traced by vmap itself
         key, sub, sel_key, mut_key = rnd.split(state.key, 4)
         parents = self._parent_pairs(state, sub)
         buf = state.next_generation
@@ -235,6 +319,8 @@ class MOEAD(Algorithm):
         return win.to(torch.int32), new_obj, z
 
     def tell(self, state, fitness):
+        if _in_vmap(state.population) or _in_vmap(fitness):
+            return self._tell_runs(state, fitness)
         win, new_obj, z = self._replace(state, fitness)
         if state.population.is_cuda and state.population.dtype == torch.float32:
             from ...ops import mo as mo_ops

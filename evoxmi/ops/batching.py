@@ -20,12 +20,15 @@ per run).  Each rule moves the run axis to the front and calls the op's batched 
 * ``ibea_truncate`` / ``spea2_truncate``: obj (B, n, m), per-row operands (B, n) → one workgroup per run, whose removal loop
   is the single-run one (n ≤ 8192, m ≤ 16 per run); SPEA2's runs each count their own removals;
 * ``cma_small_ask`` / ``cma_small_tell``: every state field (B, …) → one workgroup per run (``cma_small.hip``; d ≤ 64, λ ≤ 1024
-  per run), the recombination weights and the constants shared by the runs.
+  per run), the recombination weights and the constants shared by the runs;
+* ``moead_small_ask``: pop (B, N, d), keys (B, 2) and (B, 2, 2) → a wave per offspring, grid.y = run; ``moead_small_tell``: pop, off
+  (B, N, d), objectives (B, N, m), z (B, m) → one workgroup per run (``moead_small.hip``; N ≤ 2048, m ≤ 16 per run).  The neighbour
+  table and the weights may be shared by the runs or per run; the bounds and the rates are shared.
 
 Each run's words/trials are bit-identical to the single-run op with that run's key
 (``tests/test_batched_runs.py``), each run's sorted keys and indices to the op applied row by row
 (``tests/test_kernels_gpu.py``), each run's ranks, survivors and offspring to the single-run ops
-(``tests/test_batched_mo_gpu.py``, ``tests/test_batched_ibea_spea2_gpu.py``).  A per-run shape above a batched kernel's cap raises
+(``tests/test_batched_mo_gpu.py``, ``tests/test_batched_ibea_spea2_gpu.py``, ``tests/test_batched_moead_gpu.py``).  A per-run shape above a batched kernel's cap raises
 ``NotImplementedError``: there is no silent run-by-run fallback.  This mirrors the reference's use of ``jax.vmap`` for
 independent copies of a workflow (``run/run_de.py:54-114`` runs 32 seeds per function).
 """
@@ -197,6 +200,41 @@ def _cma_small_tell(info, in_dims, population, fitness, mean, sigma, ps, pc, C, 
     return list(out), [0] * 10
 
 
+def _shared_or_runs(x, bdim, B, per_run_dim, what):
+    """An operand the runs may share: (1, …) where unbatched or broadcast along the run axis (what ``vmap`` makes of a
+    constant that a vmapped ``init`` returned), ``_runs_of`` otherwise.  The stride test is an optimisation only: once a workflow
+    or a graph has cloned the state, the same table arrives R times and takes the per-run path, with the same bits
+    (``tests/test_batched_moead_gpu.py`` holds the shared, the broadcast and the per-run form to each other)."""
+    if bdim is None:
+        return x.unsqueeze(0).contiguous()
+    xb = x.movedim(bdim, 0)
+    if xb.stride(0) == 0 and xb.dim() == per_run_dim + 1:
+        return xb[:1].contiguous()
+    return _runs_of(x, bdim, B, per_run_dim, what)
+
+
+def _moead_small_ask(info, in_dims, pop, nb, key, kx, km, lb, ub, pro_c, dis_c, pro_m, dis_m, nm):
+    R, what = info.batch_size, "moead_small_ask vmap rule"
+    if in_dims[5] is not None or in_dims[6] is not None:
+        raise NotImplementedError(f"{what}: bounds must be shared by all runs")
+    out = _ext.ops().moead_small_ask(_runs_of(pop, in_dims[0], R, 2, what), _shared_or_runs(nb, in_dims[1], R, 2, what),
+                                     _runs_of(key, in_dims[2], R, 1, what), _runs_of(kx, in_dims[3], R, 2, what),
+                                     _runs_of(km, in_dims[4], R, 2, what), lb, ub, pro_c, dis_c, pro_m, dis_m, nm)
+    return list(out), [0, 0]
+
+
+def _moead_small_tell(info, in_dims, pop, off, pop_obj, off_obj, W, nb, z, func):
+    from .mo import check_small_caps
+
+    R, what = info.batch_size, "moead_small_tell vmap rule"
+    ob = _runs_of(off_obj, in_dims[3], R, 2, what)
+    check_small_caps(ob.shape[1], ob.shape[2], what)
+    out = _ext.ops().moead_small_tell(_runs_of(pop, in_dims[0], R, 2, what), _runs_of(off, in_dims[1], R, 2, what),
+                                      _runs_of(pop_obj, in_dims[2], R, 2, what), ob, _shared_or_runs(W, in_dims[4], R, 2, what),
+                                      _shared_or_runs(nb, in_dims[5], R, 2, what), _runs_of(z, in_dims[6], R, 1, what), func)
+    return list(out), [0, 0, 0, 0]
+
+
 def register():
     """Install the rules (idempotent).  Without the compiled extension there is nothing to
     batch: CPU tensors never reach the HIP ops, and a device op raises on its own."""
@@ -206,6 +244,7 @@ def register():
     for name, fn in (("philox_words", _philox_words), ("philox_fill", _philox_fill), ("rank_argsort_f32", _rank_argsort_f32),
                      ("de_trial", _de_trial), ("sbx", _sbx), ("pm", _pm), ("nds", _nds), ("nsga_select", _nsga_select),
                      ("ibea_fitness", _ibea_fitness), ("ibea_truncate", _ibea_truncate), ("spea2_fitness", _spea2_fitness),
-                     ("spea2_truncate", _spea2_truncate), ("cma_small_ask", _cma_small_ask), ("cma_small_tell", _cma_small_tell)):
+                     ("spea2_truncate", _spea2_truncate), ("cma_small_ask", _cma_small_ask), ("cma_small_tell", _cma_small_tell),
+                     ("moead_small_ask", _moead_small_ask), ("moead_small_tell", _moead_small_tell)):
         torch.library.register_vmap(f"evoxmi::{name}", fn)
     _REGISTERED = True

@@ -91,6 +91,9 @@ def _run(cmd):
 # sub-step (835 instructions against 704 without it in the two-chain instantiation)
 # cma_small.hip: its ask draws the normals of rng.hip bit for bit, so it takes that file's contraction mode (plain "fast" also fuses
 # inside the inlined logf / sincosf); packed f32 arithmetic is off for this file: nothing in it is written for v_pk_* issue
+# moead_small.hip: no entry on purpose.  Its runs must equal moead.hip's launches bit for bit, and PM's sum of two products
+# (evoxmi_moead.h, pm_gene) fuses the same product into the fma only when both files are compiled alike: with packed f32 arithmetic
+# switched off for this file alone the other product is fused and offspring differ in the last bit
 FILE_FLAGS = {"cma_small.hip": ["-ffp-contract=fast-honor-pragmas", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "eigh_sbr.hip": ["-fno-slp-vectorize"], "mo_geom.hip": ["-ffp-contract=fast-honor-pragmas"],
               "knea_select.hip": ["-ffp-contract=off"], "rvea_select.hip": ["-ffp-contract=off"],

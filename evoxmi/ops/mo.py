@@ -114,3 +114,56 @@ def moead_select_rows_(pop, off, win):
     """In place: pop[s] = off[win[s]] for every s with win[s] >= 0 (returns ``pop``)."""
     _ext.ops().moead_select_rows_(pop, off.contiguous(), win.to(torch.int32).contiguous())
     return pop
+
+
+# ---------------------------------------------------------------- MOEA/D at benchmark shapes, R runs per launch (moead_small.hip)
+N_CAP = 2048  # moead_small.hip, tell: one workgroup per run, a 64-bit word and a winner per slot in LDS
+M_CAP = 16  # moead_small.hip, tell: m ≤ 16 objectives (a wave per objective, the aggregation's registers)
+
+
+def check_small_caps(n: int, m: int, what: str) -> None:
+    """The per-run caps of ``moead_small_tell``; above them there is no batched form, and the solo launches for every run
+    would hide that."""
+    if n < 1 or n > N_CAP or m < 1 or m > M_CAP:
+        raise NotImplementedError(f"{what}: batched runs need 1 <= N <= {N_CAP} slots and 1 <= m <= {M_CAP} objectives per run, "
+                                  f"got N = {n}, m = {m}")
+
+
+def moead_small_ask(pop, neighbors, key, key_x, key_m, lb, ub, pro_c, dis_c, pro_m, dis_m):
+    """Parents and variation of a MOEA/D generation in one launch, a wave per offspring and the run on ``grid.y``.
+
+    ``pop`` (R, N, d) float32, ``neighbors`` (R or 1, N, T) int64 with entries in [0, N), ``key`` (R, 2), ``key_x`` / ``key_m``
+    (R, 2) the keys ``SimulatedBinary`` / ``Polynomial`` would receive, ``lb`` / ``ub`` and the rates shared by the runs; 2-D
+    operands (and keys (2,)) are a single run.  Returns ``(offspring (R, N, d), parents (R, 2, N) int32)``; run r equals
+    ``moead_parents(neighbors[r], key[r])`` and ``moead_variation`` on those parents with ``key_x[r]`` / ``key_m[r]``, bit for
+    bit.  The wave draws its two parents (the two smallest ``(u24, j)`` of its row of ``uniform(key, (N, T))``) and keeps them in
+    registers while its lanes stride over the d genes.  No cap on N or d beyond the grid; an offspring whose neighbour lies
+    outside [0, N) is a row of NaN."""
+    from . import random as rnd
+
+    n, d = pop.shape[-2], pop.shape[-1]
+    nm = n if n == 1 else (n // 2) * 2
+    lb = lb.to(device=pop.device, dtype=torch.float32).expand(d).contiguous()
+    ub = ub.to(device=pop.device, dtype=torch.float32).expand(d).contiguous()
+    split2 = lambda k: rnd.split(k, 2) if k.dim() == 1 else torch.stack([rnd.split(r, 2) for r in k])  # noqa: E731
+    kx, km = split2(key_x), split2(key_m)
+    off, parents = _ext.ops().moead_small_ask(pop.to(torch.float32).contiguous(), neighbors.to(torch.int64).contiguous(), key.contiguous(),
+                                              kx.contiguous(), km.contiguous(), lb, ub, float(pro_c), float(dis_c), float(pro_m),
+                                              float(dis_m), int(nm))
+    return off, parents
+
+
+def moead_small_tell(pop, off, pop_obj, off_obj, w, neighbors, z, func):
+    """The whole of MOEA/D's tell in one launch, one workgroup of 1024 threads per run and no reverse-neighbour CSR.
+
+    ``pop`` / ``off`` (R, N, d), ``pop_obj`` / ``off_obj`` (R, N, m), ``w`` (R or 1, N, m), ``neighbors`` (R or 1, N, T) int64,
+    ``z`` (R, m); 2-D operands are a single run.  Returns ``(new_pop, new_obj, z', win (R, N) int32)`` and writes nothing in
+    place: ``z' = minimum(z, off_obj.min(0))`` and ``z_max = pop_obj.max(0)`` (NaN propagating as torch's), then per slot the
+    first strict minimiser of the aggregate over the offspring whose neighbourhood holds the slot (lowest index on ties, −0
+    equal to +0, a NaN aggregate never a candidate), taken iff it is strictly below the occupant's aggregate; ``win`` is that
+    offspring or −1.  Run r equals ``moead_replace`` + ``moead_select_rows`` on run r's operands, bit for bit.
+    Caps: N ≤ 2048, m ≤ 16, T ≤ N per run (``N_CAP``, ``M_CAP``)."""
+    fid = MOEAD_FUNCS[func] if isinstance(func, str) else int(func)
+    f32 = lambda t: t.to(torch.float32).contiguous()  # noqa: E731
+    return tuple(_ext.ops().moead_small_tell(f32(pop), f32(off), f32(pop_obj), f32(off_obj), f32(w), neighbors.to(torch.int64).contiguous(),
+                                            f32(z), fid))

@@ -18,13 +18,13 @@
   gde3  : GDE3 pop=4096 on DTLZ2 (m=3, d=500)              — 1×MI355X
   moead : MOEA/D pop=16384 on LSMOP1 (m=3, d=10000), Tchebycheff aggregation
 
-  --runs R (nsga2, gde3, ibea, spea2): R independent seeds, the protocol of a multi-objective comparison (20–30 runs at
+  --runs R (nsga2, gde3, ibea, spea2, moead — MOEA/D then runs DTLZ2 with PBI): R independent seeds, the protocol of a multi-objective comparison (20–30 runs at
   pop 100–200).  Without --batched the R seeds run one after another, each its own workflow (and hipGraph);
   with --batched they are one BatchedRuns workflow, every launch of a generation advancing all R runs.
   Both modes start run r from split(fold_in(key, 1), R)[r], so they compute the same runs; ms_per_gen is the
   time of one generation of all R runs, and after the timed region every run's IGD is printed.
 
-python tools/bench_mo.py --algo nsga2|gde3|ibea|spea2 [--pop 100 --dim 12] --runs 32 [--batched]
+python tools/bench_mo.py --algo nsga2|gde3|ibea|spea2|moead [--pop 100 --dim 12] --runs 32 [--batched]
 python tools/bench_mo.py --algo nsga2|nsga3|sra|ibea|spea2|bceibea|knea|m2m|rvea|rveaa|lmocso|bige|tdea|moead [--gens 20] [--warmup 3] [--no-graph]
 torchrun --nproc-per-node 8 --master-addr 127.0.0.1 tools/bench_mo.py --algo moead
 
@@ -61,6 +61,9 @@ def build(args, dev):
         if args.algo == "lmocso":  # its constructor takes n_objs first
             return LMOCSO(m, lb, ub, args.pop or 4096), DTLZ2(d=d, m=m)
         return algos[args.algo](lb, ub, m, args.pop or (4000 if args.algo == "m2m" else 4096)), DTLZ2(d=d, m=m)
+    if args.runs:  # the protocol shape of --runs: DTLZ2 in the unit box, MOEA/D's default PBI aggregation
+        d = args.dim or 12
+        return MOEAD(torch.zeros(d, device=dev), torch.ones(d, device=dev), m, args.pop or 100), DTLZ2(d=d, m=m)
     d = args.dim or 10000
     lb = torch.zeros(d, device=dev)
     ub = torch.cat([torch.ones(m - 1, device=dev), 10 * torch.ones(d - m + 1, device=dev)])
@@ -139,8 +142,8 @@ def main():
     ap.add_argument("--link-gbps", type=float, default=None, help="--simulate-rank wire model: GB/s per xGMI link and direction")
     args = ap.parse_args()
     if args.runs or args.batched:
-        if args.algo not in ("nsga2", "gde3", "ibea", "spea2") or args.runs < 1 or args.gpus != 1 or args.simulate_rank is not None or args.force_dist:
-            ap.error("--runs R [--batched] needs R >= 1, --algo nsga2, gde3, ibea or spea2, and one rank")
+        if args.algo not in ("nsga2", "gde3", "ibea", "spea2", "moead") or args.runs < 1 or args.gpus != 1 or args.simulate_rank is not None or args.force_dist:
+            ap.error("--runs R [--batched] needs R >= 1, --algo nsga2, gde3, ibea, spea2 or moead, and one rank")
         return run_seeds(args, torch.device("cpu" if args.cpu else "cuda"))
     import torch.distributed as dist
     from evoxmi.parallel import init_distributed
