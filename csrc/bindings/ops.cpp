@@ -1626,20 +1626,62 @@ at::Tensor nsga3_niche_select(const at::Tensor& rank, const at::Tensor& last_ran
                               const at::Tensor& key, int64_t N, int64_t R) {
   CHECK_DEV(rank); CHECK_CONTIG(rank); CHECK_DEV(last_rank); CHECK_DEV(group); CHECK_CONTIG(group);
   CHECK_DEV(group_dist); CHECK_F32(group_dist); CHECK_CONTIG(group_dist);
-  check_key(key);
-  const int64_t n = rank.numel();
-  TORCH_CHECK(rank.scalar_type() == at::kInt && rank.dim() == 1, "nsga3_niche_select: rank int32 (n,)");
-  TORCH_CHECK(last_rank.scalar_type() == at::kInt && last_rank.numel() == 1, "nsga3_niche_select: last_rank is one int32 device word");
-  TORCH_CHECK(group.scalar_type() == at::kLong && group.dim() == 1 && group.numel() == n, "nsga3_niche_select: group int64 (n,)");
-  TORCH_CHECK(group_dist.dim() == 1 && group_dist.numel() == n, "nsga3_niche_select: group_dist float32 (n,)");
+  // rank (n,) with one key, or B runs: rank (B, n), last_rank (B,), key (B, 2), one workgroup per run
+  const bool batched = rank.dim() == 2;
+  const int64_t B = batched ? rank.size(0) : 1;
+  if (batched) {
+    TORCH_CHECK(key_batch(key, "nsga3_niche_select") == B, "nsga3_niche_select: keys must be (B, 2) for rank (B, n)");
+  } else {
+    check_key(key);
+  }
+  TORCH_CHECK(rank.scalar_type() == at::kInt && (rank.dim() == 1 || batched), "nsga3_niche_select: rank int32 (n,) or (B, n)");
+  const int64_t n = rank.size(-1);
+  TORCH_CHECK(last_rank.scalar_type() == at::kInt && last_rank.numel() == B && last_rank.is_contiguous(),
+              "nsga3_niche_select: last_rank is one int32 device word per run");
+  TORCH_CHECK(group.scalar_type() == at::kLong && group.sizes() == rank.sizes(), "nsga3_niche_select: group int64, the shape of rank");
+  TORCH_CHECK(group_dist.sizes() == rank.sizes(), "nsga3_niche_select: group_dist float32, the shape of rank");
   TORCH_CHECK(n >= 1 && n <= 8192, "nsga3_niche_select: 1 <= n <= 8192");
   TORCH_CHECK(R >= 1 && R <= 8192, "nsga3_niche_select: 1 <= R <= 8192");
   TORCH_CHECK(N >= 1 && N <= n, "nsga3_niche_select: need 1 <= N <= n");
   c10::DeviceGuard g(rank.device());
-  auto idx = at::empty({N}, rank.options().dtype(at::kLong));
-  evx_nsga3_niche_select(rank.data_ptr<int>(), last_rank.data_ptr<int>(), group.data_ptr<int64_t>(), group_dist.data_ptr<float>(),
-                         key.data_ptr<int64_t>(), (int)n, (int)N, (int)R, idx.data_ptr<int64_t>(), cur_stream());
+  auto idx = batched ? at::empty({B, N}, rank.options().dtype(at::kLong)) : at::empty({N}, rank.options().dtype(at::kLong));
+  if (B > 0)
+    evx_nsga3_niche_select(rank.data_ptr<int>(), last_rank.data_ptr<int>(), group.data_ptr<int64_t>(), group_dist.data_ptr<float>(),
+                           key.data_ptr<int64_t>(), (int)n, (int)N, (int)R, idx.data_ptr<int64_t>(), cur_stream(), (int)B);
   return idx;
+}
+
+// last_rank, group, group_dist, scale of nsga3_assoc.hip: f (n, m), rank (n,), or B runs f (B, n, m), rank (B, n); ref (K, m) shared
+std::vector<at::Tensor> nsga3_associate(const at::Tensor& f, const at::Tensor& rank, const at::Tensor& ref, int64_t N) {
+  CHECK_DEV(f); CHECK_F32(f); CHECK_CONTIG(f); CHECK_DEV(rank); CHECK_CONTIG(rank); CHECK_DEV(ref); CHECK_F32(ref); CHECK_CONTIG(ref);
+  const bool batched = f.dim() == 3;
+  TORCH_CHECK(batched || f.dim() == 2, "nsga3_associate: f float32 (n, m) or (B, n, m)");
+  const int64_t B = batched ? f.size(0) : 1, n = f.size(-2), m = f.size(-1);
+  TORCH_CHECK(rank.scalar_type() == at::kInt && rank.dim() == f.dim() - 1 && rank.size(-1) == n && (!batched || rank.size(0) == B),
+              "nsga3_associate: rank int32 (n,) or (B, n)");
+  TORCH_CHECK(ref.dim() == 2 && ref.size(1) == m, "nsga3_associate: ref float32 (K, m), shared by the runs");
+  TORCH_CHECK(rank.device() == f.device() && ref.device() == f.device(), "nsga3_associate: one device");
+  const int64_t K = ref.size(0);
+  TORCH_CHECK(n >= 1 && n <= 8192, "nsga3_associate: 1 <= n <= 8192");
+  TORCH_CHECK(m >= 1 && m <= 16, "nsga3_associate: 1 <= m <= 16");
+  TORCH_CHECK(K >= 1 && K <= 8192, "nsga3_associate: 1 <= K <= 8192");
+  TORCH_CHECK(N >= 0 && N < n, "nsga3_associate: need 0 <= N < n");
+  TORCH_CHECK(B <= 65535, "nsga3_associate: B <= 65535");
+  c10::DeviceGuard g(f.device());
+  auto lead = [&](std::vector<int64_t> shape) {
+    if (batched) shape.insert(shape.begin(), B);
+    return shape;
+  };
+  auto last_rank = at::empty(lead({}), f.options().dtype(at::kInt));
+  auto group = at::empty(lead({n}), f.options().dtype(at::kLong));
+  auto group_dist = at::empty(lead({n}), f.options());
+  auto scale = at::empty(lead({2, m}), f.options().dtype(at::kDouble));
+  auto what = at::empty({m, K}, f.options().dtype(at::kDouble));
+  if (B > 0)
+    evx_nsga3_associate(f.data_ptr<float>(), rank.data_ptr<int>(), ref.data_ptr<float>(), (int)B, (int)n, (int)m, (int)K, (int)N,
+                        what.data_ptr<double>(), last_rank.data_ptr<int>(), scale.data_ptr<double>(), group.data_ptr<int64_t>(),
+                        group_dist.data_ptr<float>(), cur_stream());
+  return {last_rank, group, group_dist, scale};
 }
 
 // part (K·S,) region-major, counts (K,), worst (K,) of m2m_select.hip: every region's NSGA-II selection of S of its rows
@@ -2189,6 +2231,7 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("cma_eig_out(Tensor Bp, Tensor w, int d, Tensor? B_out=None, Tensor? B_alt=None, Tensor? keep=None) -> Tensor[]");
   m.def("nsga_select(Tensor rank, Tensor f, int N, int mask_pos) -> Tensor");
   m.def("nsga3_niche_select(Tensor rank, Tensor last_rank, Tensor group, Tensor group_dist, Tensor key, int N, int R) -> Tensor");
+  m.def("nsga3_associate(Tensor f, Tensor rank, Tensor ref, int N) -> Tensor[]");
   m.def("m2m_select(Tensor obj, Tensor region, Tensor rad, int K, int S) -> Tensor[]");
   m.def("knea_select(Tensor obj, Tensor rank, int N, Tensor r, Tensor t, float knee_rate) -> Tensor[]");
   m.def("rvea_cos_best(Tensor A, Tensor? shift, float? floor, Tensor B, bool clamp, bool self_zero) -> Tensor[]");
@@ -2298,6 +2341,7 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("cma_eig_out", &cma_eig_out);
   m.impl("nsga_select", &nsga_select);
   m.impl("nsga3_niche_select", &nsga3_niche_select);
+  m.impl("nsga3_associate", &nsga3_associate);
   m.impl("m2m_select", &m2m_select);
   m.impl("knea_select", &knea_select);
   m.impl("rvea_cos_best", &rvea_cos_best);

@@ -242,9 +242,15 @@ void evx_cma_eig_out(const float* Bp, const float* w, int d, int np, float* B, f
 
 // nsga_select.hip: batch runs, rank (batch, n), f (batch, n, m) → keep (batch, N), one workgroup per run
 void evx_nsga_select(const int32_t* rank, const float* f, int n, int m, int N, int mask_pos, int64_t* keep, hipStream_t s, int batch = 1);
-// nsga3_select.hip: NSGA-III niche-preserving selection (n ≤ 8192, R ≤ 8192), idx (N,) ascending rows
+// nsga3_select.hip: NSGA-III niche-preserving selection (n ≤ 8192, R ≤ 8192), idx (N,) ascending rows; batch runs, one workgroup
+// per run: rank, group, group_dist (batch, n), last_rank (batch,), key (batch, 2) → idx (batch, N)
 void evx_nsga3_niche_select(const int32_t* rank, const int32_t* last_rank, const int64_t* group, const float* group_dist,
-                            const int64_t* key, int n, int N, int R, int64_t* idx, hipStream_t s);
+                            const int64_t* key, int n, int N, int R, int64_t* idx, hipStream_t s, int batch = 1);
+// nsga3_assoc.hip: NSGA-III's normalisation and association in three launches (the contract is in evoxmi/ops/nsga3.py; n ≤ 8192,
+// m ≤ 16, N < n; B runs, the K reference points shared): f (B, n, m), rank (B, n), ref (K, m) → last_rank (B,), scale (B, 2, m) the
+// ideal point and the nadir, group (B, n) and group_dist (B, n); what is a float64 scratch of m·K words
+void evx_nsga3_associate(const float* f, const int32_t* rank, const float* ref, int B, int n, int m, int K, int N, double* what,
+                         int32_t* last_rank, double* scale, int64_t* group, float* group_dist, hipStream_t s);
 // m2m_select.hip: MOEA/D-M2M's per-region NSGA-II selection, one workgroup per region (n ≤ 8192, m ≤ 16, K ≤ 1024);
 // region is (n,) int64 when region64 else int32, part (K·S,) region-major, counts and worst (K,)
 void evx_m2m_select(const float* f, const void* region, int region64, const int64_t* rad, int n, int m, int K, int S,

@@ -2,6 +2,9 @@
 // reference algorithms/mo/nsga3.py:93-211, whose sequential while_loop the Python side
 // already reformulates as "keep the K smallest (ρ_j + k, j)").
 //
+// B independent runs take one workgroup each (blockIdx.x = run): rank, group, group_dist are (B, n), last_rank (B,), key (B, 2),
+// idx (B, N); B = 1 is the single-run launch.
+//
 // Inputs per merged row i < n: its Pareto rank, its niche group_i ∈ [0, R) and the
 // perpendicular distance group_dist_i to that niche's reference line; last_rank is a device
 // word.  front = rank < last_rank survives outright, last = rank == last_rank are the
@@ -82,7 +85,14 @@ __global__ void __launch_bounds__(NS_THREADS) nsga3_niche_select_kernel(const in
   __shared__ NicheShared<IT> sh;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int base = t * IT;
-  const int lr = *last_rank;
+  // one workgroup per run: every per-run operand is offset by the run index, nothing else changes
+  const int run = blockIdx.x;
+  rank += (size_t)run * n;
+  group += (size_t)run * n;
+  group_dist += (size_t)run * n;
+  key += 2 * run;
+  idx += (size_t)run * N;
+  const int lr = last_rank[run];
 
   for (int j = t; j < NS_MAX; j += NS_THREADS) {
     sh.rc[j] = 0u;
@@ -230,13 +240,13 @@ __global__ void __launch_bounds__(NS_THREADS) nsga3_niche_select_kernel(const in
 }  // namespace
 
 void evx_nsga3_niche_select(const int32_t* rank, const int32_t* last_rank, const int64_t* group, const float* group_dist,
-                            const int64_t* key, int n, int N, int R, int64_t* idx, hipStream_t s) {
+                            const int64_t* key, int n, int N, int R, int64_t* idx, hipStream_t s, int batch) {
   if (n <= NS_THREADS)
-    nsga3_niche_select_kernel<1><<<1, NS_THREADS, 0, s>>>(rank, last_rank, group, group_dist, key, n, N, R, idx);
+    nsga3_niche_select_kernel<1><<<batch, NS_THREADS, 0, s>>>(rank, last_rank, group, group_dist, key, n, N, R, idx);
   else if (n <= 2 * NS_THREADS)
-    nsga3_niche_select_kernel<2><<<1, NS_THREADS, 0, s>>>(rank, last_rank, group, group_dist, key, n, N, R, idx);
+    nsga3_niche_select_kernel<2><<<batch, NS_THREADS, 0, s>>>(rank, last_rank, group, group_dist, key, n, N, R, idx);
   else if (n <= 4 * NS_THREADS)
-    nsga3_niche_select_kernel<4><<<1, NS_THREADS, 0, s>>>(rank, last_rank, group, group_dist, key, n, N, R, idx);
+    nsga3_niche_select_kernel<4><<<batch, NS_THREADS, 0, s>>>(rank, last_rank, group, group_dist, key, n, N, R, idx);
   else
-    nsga3_niche_select_kernel<8><<<1, NS_THREADS, 0, s>>>(rank, last_rank, group, group_dist, key, n, N, R, idx);
+    nsga3_niche_select_kernel<8><<<batch, NS_THREADS, 0, s>>>(rank, last_rank, group, group_dist, key, n, N, R, idx);
 }

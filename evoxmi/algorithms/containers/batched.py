@@ -40,7 +40,14 @@ reference points, replaces without a reverse-neighbour CSR and selects the rows 
 pipeline, float32 and at most 2048 subproblems and 16 objectives per run (``NotImplementedError`` otherwise); on the CPU its tell runs
 run by run inside a Python-registered op.  ``MOEADDRA``, ``EAGMOEAD`` and ``MOEADM2M`` are not covered.
 
-Covered multi-objective algorithms: NSGA-II, GDE3, IBEA, SPEA2, MOEA/D.  The others are not, and an uncovered one is not
+NSGA-III batches (``tests/test_batched_nsga3.py``, ``tests/test_nsga3_assoc_gpu.py``): after the batched non-dominated sort its tell is
+four launches that take a run index — one workgroup per run finds the last rank, the ideal point, the extremes and the nadir, a grid row
+per run associates every row with its reference point (``nsga3_assoc.hip``, float64, no (n, K) array), and one workgroup per run does
+the niching (``nsga3_select.hip``) — for merged populations of at most 8192 rows, 8 objectives and 8192 reference points per run
+(``NotImplementedError`` above).  The solo algorithm runs the same kernels, so run r is bit-identical to it.  On the CPU the tell's
+selection runs run by run inside a Python-registered op (``evoxmi.ops.nsga3.survivors_run``).
+
+Covered multi-objective algorithms: NSGA-II, GDE3, IBEA, SPEA2, MOEA/D, NSGA-III.  The others are not, and an uncovered one is not
 guaranteed to raise.  Most raise from ``vmap`` (their selections read the host or loop on data), but RVEA runs and its
 runs differ from solo runs: do not rely on ``BatchedRuns`` over an algorithm that is not listed here.
 """

@@ -15,8 +15,13 @@ smallest (ρ_j + k, j) are kept.  Same distribution, no data-dependent loop.
 
 That selection is ``ops.nds.nsga3_survivors``: one launch of ``nsga3_select.hip`` on the
 device (merged population ≤ 8192 rows, ≤ 8192 reference points), the same steps in
-fixed-shape torch on the CPU and above those caps.  Neither reads anything on the host, so
-a whole generation is captured into one hipGraph (``StdWorkflow(..., graph=True)``).
+fixed-shape torch on the CPU and above those caps.  The normalisation and the association
+before it are ``ops.nsga3.associate``: three launches of ``nsga3_assoc.hip`` on the device
+(float64, no (n, K) array; ≤ 16 objectives), the float32 torch expressions on the CPU and above
+the caps.  Nothing reads the host, so a whole generation is captured into one hipGraph
+(``StdWorkflow(..., graph=True)``), and every kernel takes a run index, so ``BatchedRuns(NSGA3)``
+advances R seeds with the launches of one (merged population ≤ 8192 rows and ≤ 8 objectives per
+run, the caps of the batched non-dominated sort); run r is bit-identical to the algorithm alone.
 """
 from __future__ import annotations
 
@@ -26,9 +31,9 @@ from ...core import State
 from ...operators import selection
 from ...operators.sampling import UniformSampling
 from ...operators.selection.non_dominate import non_dominated_sort
+from ...ops import nsga3 as nsga3_ops
 from ...ops import random as rnd
-from ...ops.nds import nsga3_survivors
-from ...utils.common import cos_dist
+from ...ops.nds import _in_vmap, nsga3_survivors
 from .common import MOAlgorithm
 
 
@@ -46,30 +51,17 @@ class NSGA3(MOAlgorithm):
         return off, state.update(next_generation=off, key=key)
 
     def tell(self, state, fitness):
-        N, m = self.pop_size, self.n_objs
+        N = self.pop_size
         merged_pop = torch.cat([state.population, state.next_generation], 0)
         merged_fit = torch.cat([state.fitness, fitness], 0)
-        n = merged_fit.shape[0]
-        rank = non_dominated_sort(merged_fit, until=N + 1)
-        last_rank = torch.sort(rank).values[N]  # 0-d view: no host sync (capturable)
-        valid = rank <= last_rank
-        inf = torch.full_like(merged_fit, float("inf"))
-        ideal = torch.where(valid[:, None], merged_fit, inf).min(0).values
-        Fn = merged_fit - ideal
-        weight = torch.eye(m, device=Fn.device) + 1e-6
-        asf = (Fn[None, :, :] / weight[:, None, :]).amax(-1)  # (m, n)
-        asf = torch.where(valid[None, :], asf, torch.full_like(asf, float("inf")))
-        extreme = Fn[torch.argmin(asf, 1)]
-        sol, info = torch.linalg.solve_ex(extreme, torch.ones(m, 1, device=Fn.device))
-        intercept = 1.0 / sol[:, 0]
-        worst = torch.where(valid[:, None], Fn, -inf).max(0).values
-        ok = (info == 0) & torch.isfinite(intercept).all() & (intercept > 1e-6).all()
-        nadir = torch.where(ok, intercept, worst)
-        Fn = Fn / nadir
-        cosine = cos_dist(Fn, self.ref).clamp(-1, 1)
-        dist = torch.linalg.norm(Fn, dim=-1, keepdim=True) * torch.sqrt(torch.clamp(1 - cosine**2, min=0))
-        group_dist, group = dist.min(1)
-        # niche-preserving selection from the last front: nsga3_select.hip on the device
-        idx = nsga3_survivors(rank, last_rank, group, group_dist, state.key, N, self.ref.shape[0])
+        if not merged_fit.is_cuda and _in_vmap(merged_fit):
+            # a run of BatchedRuns on the CPU: vmap cannot trace the peel loop, the selection goes run by run inside one op
+            idx = nsga3_ops.survivors_run(merged_fit, state.key, self.ref, N)
+        else:
+            rank = non_dominated_sort(merged_fit, until=N + 1)
+            # normalisation and association: nsga3_assoc.hip on the device, the torch expressions on the CPU
+            last_rank, group, group_dist, _ = nsga3_ops.associate(merged_fit, rank, self.ref, N)
+            # niche-preserving selection from the last front: nsga3_select.hip on the device
+            idx = nsga3_survivors(rank, last_rank, group, group_dist, state.key, N, self.ref.shape[0])
         key, _ = rnd.split(state.key)
         return state.update(population=merged_pop[idx], fitness=merged_fit[idx], key=key)

@@ -23,12 +23,15 @@ per run).  Each rule moves the run axis to the front and calls the op's batched 
   per run), the recombination weights and the constants shared by the runs;
 * ``moead_small_ask``: pop (B, N, d), keys (B, 2) and (B, 2, 2) → a wave per offspring, grid.y = run; ``moead_small_tell``: pop, off
   (B, N, d), objectives (B, N, m), z (B, m) → one workgroup per run (``moead_small.hip``; N ≤ 2048, m ≤ 16 per run).  The neighbour
-  table and the weights may be shared by the runs or per run; the bounds and the rates are shared.
+  table and the weights may be shared by the runs or per run; the bounds and the rates are shared;
+* ``nsga3_associate``: f (B, n, m), rank (B, n) → one workgroup per run normalises, grid.y = run associates
+  (``nsga3_assoc.hip``; n ≤ 8192, m ≤ 16, K ≤ 8192 per run), the reference points shared by the runs; ``nsga3_niche_select``:
+  rank, group, group_dist (B, n), last_rank (B,), keys (B, 2) → one workgroup per run (``nsga3_select.hip``).
 
 Each run's words/trials are bit-identical to the single-run op with that run's key
 (``tests/test_batched_runs.py``), each run's sorted keys and indices to the op applied row by row
 (``tests/test_kernels_gpu.py``), each run's ranks, survivors and offspring to the single-run ops
-(``tests/test_batched_mo_gpu.py``, ``tests/test_batched_ibea_spea2_gpu.py``, ``tests/test_batched_moead_gpu.py``).  A per-run shape above a batched kernel's cap raises
+(``tests/test_batched_mo_gpu.py``, ``tests/test_batched_ibea_spea2_gpu.py``, ``tests/test_batched_moead_gpu.py``, ``tests/test_nsga3_assoc_gpu.py``).  A per-run shape above a batched kernel's cap raises
 ``NotImplementedError``: there is no silent run-by-run fallback.  This mirrors the reference's use of ``jax.vmap`` for
 independent copies of a workflow (``run/run_de.py:54-114`` runs 32 seeds per function).
 """
@@ -235,6 +238,29 @@ def _moead_small_tell(info, in_dims, pop, off, pop_obj, off_obj, W, nb, z, func)
     return list(out), [0, 0, 0, 0]
 
 
+def _nsga3_associate(info, in_dims, f, rank, ref, N):
+    from .nsga3 import check_batched_caps
+
+    B, what = info.batch_size, "nsga3_associate vmap rule"
+    if in_dims[2] is not None:
+        raise NotImplementedError(f"{what}: the reference points must be shared by all runs")
+    fb = _runs_of(f, in_dims[0], B, 2, what)
+    check_batched_caps(fb.shape[1], fb.shape[2], ref.shape[0], what)
+    return list(_ext.ops().nsga3_associate(fb, _runs_of(rank, in_dims[1], B, 1, what), ref, N)), [0, 0, 0, 0]
+
+
+def _nsga3_niche_select(info, in_dims, rank, last_rank, group, group_dist, key, N, R):
+    from .nds import NICHE_SELECT_CAP
+
+    B, what = info.batch_size, "nsga3_niche_select vmap rule"
+    rb = _runs_of(rank, in_dims[0], B, 1, what)
+    if rb.shape[1] > NICHE_SELECT_CAP or R > NICHE_SELECT_CAP:
+        raise NotImplementedError(f"{what}: batched runs need n <= {NICHE_SELECT_CAP} rows and R <= {NICHE_SELECT_CAP} reference "
+                                  f"points per run, got n = {rb.shape[1]}, R = {R}")
+    return _ext.ops().nsga3_niche_select(rb, _runs_of(last_rank, in_dims[1], B, 0, what), _runs_of(group, in_dims[2], B, 1, what),
+                                         _runs_of(group_dist, in_dims[3], B, 1, what), _runs_of(key, in_dims[4], B, 1, what), N, R), 0
+
+
 def register():
     """Install the rules (idempotent).  Without the compiled extension there is nothing to
     batch: CPU tensors never reach the HIP ops, and a device op raises on its own."""
@@ -245,6 +271,7 @@ def register():
                      ("de_trial", _de_trial), ("sbx", _sbx), ("pm", _pm), ("nds", _nds), ("nsga_select", _nsga_select),
                      ("ibea_fitness", _ibea_fitness), ("ibea_truncate", _ibea_truncate), ("spea2_fitness", _spea2_fitness),
                      ("spea2_truncate", _spea2_truncate), ("cma_small_ask", _cma_small_ask), ("cma_small_tell", _cma_small_tell),
-                     ("moead_small_ask", _moead_small_ask), ("moead_small_tell", _moead_small_tell)):
+                     ("moead_small_ask", _moead_small_ask), ("moead_small_tell", _moead_small_tell),
+                     ("nsga3_associate", _nsga3_associate), ("nsga3_niche_select", _nsga3_niche_select)):
         torch.library.register_vmap(f"evoxmi::{name}", fn)
     _REGISTERED = True

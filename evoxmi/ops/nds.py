@@ -199,11 +199,20 @@ def nsga3_survivors(rank: torch.Tensor, last_rank: torch.Tensor, group: torch.Te
     ``uniform(key)`` over the candidates.  ``last_rank`` is a 0-d tensor on the device of
     ``rank``: nothing is read on the host, so the call is capturable.  On a HIP device with
     n ≤ 8192 and R ≤ 8192 it is one launch of ``nsga3_select.hip``; otherwise fixed-shape torch.
-    """
+
+    ``rank``, ``group``, ``group_dist`` of shape (B, n) with ``last_rank`` (B,) and ``key`` (B, 2) are B independent
+    runs: survivors (B, N), row b being the 1-D call on run b; on a device one launch with a workgroup per run
+    (above the caps there is no batched form: ``NotImplementedError``, also for a run under ``vmap``)."""
     N, R = int(N), int(R)
-    n = rank.shape[0]
+    n = rank.shape[-1]
     group_dist = group_dist.to(torch.float32)
+    if rank.dim() == 2 and not rank.is_cuda:
+        return torch.stack([_nsga3_survivors_torch(rank[b], last_rank[b], group[b].to(torch.int64), group_dist[b], key[b], N, R)
+                            for b in range(rank.shape[0])])
+    if rank.is_cuda and (rank.dim() == 2 or _in_vmap(rank)) and (n > NICHE_SELECT_CAP or R > NICHE_SELECT_CAP):
+        raise NotImplementedError(f"nsga3_survivors: batched runs need n <= {NICHE_SELECT_CAP} rows and R <= {NICHE_SELECT_CAP} "
+                                  f"reference points per run, got n = {n}, R = {R}")
     if rank.is_cuda and n <= NICHE_SELECT_CAP and R <= NICHE_SELECT_CAP:
-        return _ext.ops().nsga3_niche_select(rank.to(torch.int32).contiguous(), last_rank.to(torch.int32), group.to(torch.int64).contiguous(),
+        return _ext.ops().nsga3_niche_select(rank.to(torch.int32).contiguous(), last_rank.to(torch.int32).contiguous(), group.to(torch.int64).contiguous(),
                                              group_dist.contiguous(), key.to(rank.device).contiguous(), N, R)
     return _nsga3_survivors_torch(rank, last_rank, group.to(torch.int64), group_dist, key, N, R)
