@@ -2171,12 +2171,40 @@ at::Tensor hv_contrib(const at::Tensor& S, const at::Tensor& P, const at::Tensor
   return f;
 }
 
+// f (n,) of hype_fitness.hip for points (n, m), ref (m), key (2,), or B runs: points (B, n, m), ref (B, m), key (B, 2) → f (B, n);
+// alpha (≥ n entries) is shared by the runs
+at::Tensor hype_fitness(const at::Tensor& points, const at::Tensor& ref, const at::Tensor& alpha, const at::Tensor& key, int64_t n_sample) {
+  for (auto* t : {&points, &ref, &alpha}) { CHECK_DEV(*t); CHECK_F32(*t); CHECK_CONTIG(*t); }
+  const bool batched = points.dim() == 3;
+  TORCH_CHECK(batched || points.dim() == 2, "hype_fitness: points float32 (n, m) or (B, n, m)");
+  const int64_t B = batched ? points.size(0) : 1, n = points.size(-2), m = points.size(-1);
+  if (batched) {
+    TORCH_CHECK(key_batch(key, "hype_fitness") == B, "hype_fitness: keys must be (B, 2) for points (B, n, m)");
+    TORCH_CHECK(ref.dim() == 2 && ref.size(0) == B && ref.size(1) == m, "hype_fitness: ref (B, m) for points (B, n, m)");
+  } else {
+    check_key(key);
+    TORCH_CHECK(key.dim() == 1 && ref.dim() == 1 && ref.size(0) == m, "hype_fitness: key (2,) and ref (m,) for points (n, m)");
+  }
+  TORCH_CHECK(key.device() == points.device() && ref.device() == points.device() && alpha.device() == points.device(),
+              "hype_fitness: every operand on the device of points");
+  TORCH_CHECK(evx_hype_fused_ok(n, m, n_sample), "hype_fitness: needs 1 <= n <= 2048, 1 <= m <= 16, 1 <= n_sample <= 2^20, got n = ", n,
+              ", m = ", m, ", n_sample = ", n_sample);
+  TORCH_CHECK(alpha.dim() == 1 && alpha.numel() >= n, "hype_fitness: alpha needs n entries");
+  c10::DeviceGuard g(points.device());
+  auto f = batched ? at::empty({B, n}, points.options()) : at::empty({n}, points.options());
+  auto aux = at::empty({B, n_sample + m}, points.options());
+  evx_hype_fitness(points.data_ptr<float>(), ref.data_ptr<float>(), alpha.data_ptr<float>(), key.data_ptr<int64_t>(), (int)B, (int)n, (int)m,
+                   (int)n_sample, aux.data_ptr<float>(), f.data_ptr<float>(), cur_stream());
+  return f;
+}
+
 TORCH_LIBRARY(evoxmi, m) {
   m.def("es_noise_grad(Tensor key, Tensor w, int d, int row0, int col0=0, int dtot=0) -> Tensor");
   m.def("es_population(Tensor key, Tensor center, float sigma, int rows, int half, int row0, int col0=0, int dtot=0) -> Tensor");
   m.def("knn(Tensor X, Tensor Y, int T) -> Tensor[]");
   m.def("hv_count(Tensor S, Tensor P, int strict) -> Tensor");
   m.def("hv_contrib(Tensor S, Tensor P, Tensor count, Tensor alpha) -> Tensor");
+  m.def("hype_fitness(Tensor points, Tensor ref, Tensor alpha, Tensor key, int n_sample) -> Tensor");
   m.def("philox_fill(Tensor key, int n, int dist, int offset) -> Tensor");
   m.def("philox_window(Tensor key, int rows, int dtot, int col0, int own, int row0, int dist) -> Tensor");
   m.def("rank_argsort_f32(Tensor keys, int descending) -> Tensor[]");
@@ -2372,6 +2400,7 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("knn", &knn);
   m.impl("hv_count", &hv_count);
   m.impl("hv_contrib", &hv_contrib);
+  m.impl("hype_fitness", &hype_fitness);
   m.impl("sbr_symstats_out", &sbr_symstats_out);
   m.impl("sbr_symstats", &sbr_symstats);
   m.impl("sbr16_block", &sbr16_block);

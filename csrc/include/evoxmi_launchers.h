@@ -406,6 +406,13 @@ void evx_hv_count(const float* S, const float* P, int ns, int np, int m, int str
 void evx_hv_contrib(const float* S, const float* P, const int32_t* count, const float* alpha, int ns, int np, int m, float* f,
                     hipStream_t s);
 
+// hype_fitness.hip: HypE's Monte-Carlo fitness of B runs with no sample array (the contract is in the file's header and in
+// evoxmi/ops/geom.py).  P (B, n, m), ref (B, m), alpha (n) shared, key (B, 2), aux B · (n_sample + m) floats of scratch, f (B, n).
+// evx_hype_fused_ok: the shapes the launcher takes (1 ≤ n ≤ 2048, 1 ≤ m ≤ 16, 1 ≤ n_sample ≤ 2^20)
+bool evx_hype_fused_ok(int64_t n, int64_t m, int64_t n_sample);
+void evx_hype_fitness(const float* P, const float* ref, const float* alpha, const int64_t* key, int B, int n, int m, int n_sample,
+                      float* aux, float* f, hipStream_t s);
+
 // batched linear-kernel GP hyper-parameter fits (gp_fit.hip, IM-MOEA)
 void evx_linear_gp_fit(const double* a, const double* b, const double* c, const double* n, int64_t models, int steps, double lr,
                        float* v, float* s2, hipStream_t s);

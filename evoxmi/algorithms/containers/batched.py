@@ -47,7 +47,13 @@ the niching (``nsga3_select.hip``) — for merged populations of at most 8192 ro
 (``NotImplementedError`` above).  The solo algorithm runs the same kernels, so run r is bit-identical to it.  On the CPU the tell's
 selection runs run by run inside a Python-registered op (``evoxmi.ops.nsga3.survivors_run``).
 
-Covered multi-objective algorithms: NSGA-II, GDE3, IBEA, SPEA2, MOEA/D, NSGA-III.  The others are not, and an uncovered one is not
+HypE batches (``tests/test_batched_hype.py``, ``tests/test_batched_hype_gpu.py``): its Monte-Carlo fitness is ``ops.geom.hype_fitness``, on a
+HIP device the two launches of ``hype_fitness.hip`` with the run on ``grid.y`` (no sample array; merged populations of at most 2048 rows,
+16 objectives and 2^20 samples per run, and the non-dominated sort's 8192 rows and 8 objectives; ``NotImplementedError`` above), bit-identical
+to the two-pass path it replaces, so the solo trajectory did not move.  On the CPU its non-dominated sort runs run by run inside a
+Python-registered op (``evoxmi.ops.nds.rank_under_vmap``).
+
+Covered multi-objective algorithms: NSGA-II, GDE3, IBEA, SPEA2, MOEA/D, NSGA-III, HypE.  The others are not, and an uncovered one is not
 guaranteed to raise.  Most raise from ``vmap`` (their selections read the host or loop on data), but RVEA runs and its
 runs differ from solo runs: do not rely on ``BatchedRuns`` over an algorithm that is not listed here.
 """

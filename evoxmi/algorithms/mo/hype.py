@@ -11,8 +11,8 @@ import torch
 
 from ...core import State
 from ...operators import selection
-from ...operators.selection.non_dominate import lexsort, non_dominated_sort
-from ...ops import geom
+from ...operators.selection.non_dominate import lexsort
+from ...ops import geom, nds
 from ...ops import random as rnd
 from .common import MOAlgorithm
 
@@ -22,10 +22,10 @@ def cal_hv(points, ref, k, n_sample, key):
     j = torch.arange(1, n, dtype=torch.float32, device=points.device)
     alpha = torch.cumprod(torch.cat([torch.ones(1, device=points.device), (k - j) / (n - j)]), 0) / torch.arange(1, n + 1, device=points.device)
     f_min = points.min(0).values
-    samples = rnd.uniform(key, (n_sample, m)).to(points.device) * (ref - f_min) + f_min
-    # K18: per-sample dominator counts, then per-point Σ α[count − 1] (two kernels on the GPU)
-    cnt = geom.hv_count(samples, points, strict=False)
-    f = geom.hv_contrib(samples, points, cnt, alpha)
+    # per-sample dominator counts, then per-point Σ α[count − 1] over samples drawn between f_min and ref: on a HIP device
+    # hype_fitness.hip, which writes no sample array and takes a run axis (BatchedRuns); elsewhere K18's two passes.  Both
+    # give the same bits (ops.geom.hype_fitness)
+    f = geom.hype_fitness(points, ref, alpha, key, n_sample)
     return f * torch.prod(ref - f_min) / n_sample
 
 
@@ -54,7 +54,7 @@ class HypE(MOAlgorithm):
         merged_pop = torch.cat([state.population, state.next_generation], 0)
         merged_obj = torch.cat([state.fitness, fitness], 0)
         n = merged_obj.shape[0]
-        rank = non_dominated_sort(merged_obj)
+        rank = nds.rank_under_vmap(merged_obj)  # non_dominated_sort, run by run where BatchedRuns vmaps the CPU path
         worst = rank.max()
         key, sub = rnd.split(state.key)
         hv = cal_hv(merged_obj, state.ref_point, n, self.n_sample, sub)

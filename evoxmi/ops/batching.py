@@ -26,7 +26,10 @@ per run).  Each rule moves the run axis to the front and calls the op's batched 
   table and the weights may be shared by the runs or per run; the bounds and the rates are shared;
 * ``nsga3_associate``: f (B, n, m), rank (B, n) → one workgroup per run normalises, grid.y = run associates
   (``nsga3_assoc.hip``; n ≤ 8192, m ≤ 16, K ≤ 8192 per run), the reference points shared by the runs; ``nsga3_niche_select``:
-  rank, group, group_dist (B, n), last_rank (B,), keys (B, 2) → one workgroup per run (``nsga3_select.hip``).
+  rank, group, group_dist (B, n), last_rank (B,), keys (B, 2) → one workgroup per run (``nsga3_select.hip``);
+* ``hype_fitness``: points (B, n, m), ref (B, m), keys (B, 2) → grid.y = run in both kernels (``hype_fitness.hip``; n ≤ 2048, m ≤ 16,
+  n_sample ≤ 2^20 per run), α shared by the runs.  ``hv_count`` and ``hv_contrib`` have no batched form: their rules pass unbatched
+  calls through and raise on batched operands (``tests/test_hype_fitness_gpu.py``).
 
 Each run's words/trials are bit-identical to the single-run op with that run's key
 (``tests/test_batched_runs.py``), each run's sorted keys and indices to the op applied row by row
@@ -261,6 +264,33 @@ def _nsga3_niche_select(info, in_dims, rank, last_rank, group, group_dist, key, 
                                          _runs_of(group_dist, in_dims[3], B, 1, what), _runs_of(key, in_dims[4], B, 1, what), N, R), 0
 
 
+def _hype_fitness(info, in_dims, points, ref, alpha, key, n_sample):
+    from .geom import hype_fused_ok
+
+    B, what = info.batch_size, "hype_fitness vmap rule"
+    if in_dims[2] is not None:
+        raise NotImplementedError(f"{what}: alpha must be shared by all runs")
+    if in_dims[0] is None and in_dims[1] is None and in_dims[3] is None:
+        return _ext.ops().hype_fitness(points, ref, alpha, key, n_sample), None
+    pb = _runs_of(points, in_dims[0], B, 2, what)
+    if not hype_fused_ok(pb.shape[1], pb.shape[2], n_sample):
+        raise NotImplementedError(f"{what}: batched runs need n <= 2048, m <= 16 and n_sample <= 2^20 per run, got n = {pb.shape[1]}, "
+                                  f"m = {pb.shape[2]}, n_sample = {n_sample}")
+    return _ext.ops().hype_fitness(pb, _runs_of(ref, in_dims[1], B, 1, what), alpha, _runs_of(key, in_dims[3], B, 1, what), n_sample), 0
+
+
+def _hv_count(info, in_dims, S, P, strict):
+    if in_dims[0] is not None or in_dims[1] is not None:
+        raise NotImplementedError("hv_count vmap rule: no batched form (HypE's batched runs go through hype_fitness, within its caps)")
+    return _ext.ops().hv_count(S, P, strict), None
+
+
+def _hv_contrib(info, in_dims, S, P, count, alpha):
+    if any(d is not None for d in in_dims):
+        raise NotImplementedError("hv_contrib vmap rule: no batched form (HypE's batched runs go through hype_fitness, within its caps)")
+    return _ext.ops().hv_contrib(S, P, count, alpha), None
+
+
 def register():
     """Install the rules (idempotent).  Without the compiled extension there is nothing to
     batch: CPU tensors never reach the HIP ops, and a device op raises on its own."""
@@ -272,6 +302,7 @@ def register():
                      ("ibea_fitness", _ibea_fitness), ("ibea_truncate", _ibea_truncate), ("spea2_fitness", _spea2_fitness),
                      ("spea2_truncate", _spea2_truncate), ("cma_small_ask", _cma_small_ask), ("cma_small_tell", _cma_small_tell),
                      ("moead_small_ask", _moead_small_ask), ("moead_small_tell", _moead_small_tell),
-                     ("nsga3_associate", _nsga3_associate), ("nsga3_niche_select", _nsga3_niche_select)):
+                     ("nsga3_associate", _nsga3_associate), ("nsga3_niche_select", _nsga3_niche_select),
+                     ("hype_fitness", _hype_fitness), ("hv_count", _hv_count), ("hv_contrib", _hv_contrib)):
         torch.library.register_vmap(f"evoxmi::{name}", fn)
     _REGISTERED = True

@@ -88,6 +88,7 @@ def _run(cmd):
 # penalised distance bit for bit
 # nsga3_assoc.hip: the same kind of contract (NSGA-III's nadir and perpendicular distances), and the solo and the batched call
 # share its kernels bit for bit; it is float64 throughout, so packed f32 arithmetic is switched off for it
+# hype_fitness.hip: its samples are u · (ref − fmin) + fmin with two roundings, bit for bit the torch expression they replace
 # hv_exact.hip: its accuracy contract counts one rounding per float64 operation of the stated formulas, so none may fuse
 # planar_rollout.hip: its sub-step is scalar f32 arithmetic; SLP packing adds ~190 v_mov per
 # sub-step (835 instructions against 704 without it in the two-chain instantiation)
@@ -101,7 +102,8 @@ FILE_FLAGS = {"cma_small.hip": ["-ffp-contract=fast-honor-pragmas", "-Xclang", "
               "knea_select.hip": ["-ffp-contract=off"], "rvea_select.hip": ["-ffp-contract=off"],
               "bige_select.hip": ["-ffp-contract=off"], "tdea_select.hip": ["-ffp-contract=off"],
               "nsga3_assoc.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
-              "hv_exact.hip": ["-ffp-contract=off"], "rng.hip": ["-ffp-contract=fast-honor-pragmas"],
+              "hv_exact.hip": ["-ffp-contract=off"], "hype_fitness.hip": ["-ffp-contract=off"],
+              "rng.hip": ["-ffp-contract=fast-honor-pragmas"],
               "neuro.hip": ["-fno-slp-vectorize"], "planar_rollout.hip": ["-fno-slp-vectorize"], "gemm_ks.hip": ["-fno-slp-vectorize"]}
 
 

@@ -11,6 +11,7 @@ import torch
 from . import _ext
 
 KNN_MAX_T, KNN_MAX_M, HV_MAX_M = 32, 64, 16
+HYPE_MAX_N, HYPE_MAX_SAMPLES = 2048, 1 << 20  # hype_fitness.hip: rows and samples per run
 
 
 def _sqdist_rows(X, Y, chunk=512):
@@ -79,3 +80,40 @@ def hv_contrib(samples: torch.Tensor, points: torch.Tensor, count: torch.Tensor,
         dom = (points[:, None, :] <= s[None, :, :]).all(-1)
         f = f + torch.where(dom, w[s0 : s0 + 2048][None, :], torch.zeros((), device=f.device)).sum(1)
     return f
+
+
+def hype_fused_ok(n: int, m: int, n_sample: int) -> bool:
+    """The per-run shapes ``hype_fitness.hip`` takes (``evx_hype_fused_ok`` checks the same in the op)."""
+    return 1 <= n <= HYPE_MAX_N and 1 <= m <= HV_MAX_M and 1 <= n_sample <= HYPE_MAX_SAMPLES
+
+
+def hype_fitness(points: torch.Tensor, ref: torch.Tensor, alpha: torch.Tensor, key: torch.Tensor, n_sample: int) -> torch.Tensor:
+    """HypE's unscaled Monte-Carlo fitness ``f_i = Σ_s [p_i ≤ x_s in every objective] · α[c_s − 1]`` with
+    ``c_s = #{i : p_i ≤ x_s}`` (terms with ``c_s = 0`` drop out) over the samples
+    ``x = uniform(key, (n_sample, m)) * (ref − f_min) + f_min``, ``f_min`` the column minimum of ``points``.
+
+    ``points`` (n, m), ``ref`` (m,), ``key`` (2,) give ``f`` (n,); ``points`` (B, n, m), ``ref`` (B, m), ``key`` (B, 2) are B
+    independent runs and give (B, n), row b being the call on run b.  ``alpha`` (n,) is shared by the runs.
+
+    Contract: ``f`` equals bit for bit ``hv_contrib(x, points, hv_count(x, points, False), alpha)``.  On a HIP device, for
+    float32 operands with ``hype_fused_ok(n, m, n_sample)``, that is two launches of ``hype_fitness.hip`` for all B runs which
+    write no sample array: sample s, objective k is element ``s·m + k`` of the Philox stream of ``key`` (same block, word and
+    24-bit mapping as ``random.uniform``), scaled in float32 with two roundings; partial t of 256 adds the terms of
+    ``s = t, t + 256, …`` in increasing s from 0 and the partials reduce by the tree ``o = 128, …, 1``, which is
+    ``hv_contrib``'s order.  Everywhere else (CPU tensors, other dtypes, shapes outside the caps) it is that composition itself,
+    run by run for 3-D points."""
+    n_sample = int(n_sample)
+    n, m = points.shape[-2:]
+    if points.is_cuda and key.device == points.device and points.dtype == ref.dtype == alpha.dtype == torch.float32:
+        if hype_fused_ok(n, m, n_sample):
+            return _ext.ops().hype_fitness(points.contiguous(), ref.contiguous(), alpha.contiguous(), key.contiguous(), n_sample)
+        if points.dim() == 3:
+            raise NotImplementedError(f"hype_fitness: batched runs need n <= {HYPE_MAX_N}, m <= {HV_MAX_M} and n_sample <= "
+                                      f"{HYPE_MAX_SAMPLES} per run, got n = {n}, m = {m}, n_sample = {n_sample}")
+    if points.dim() == 3:
+        return torch.stack([hype_fitness(p, r, alpha, k, n_sample) for p, r, k in zip(points, ref, key)])
+    from . import random as rnd
+
+    f_min = points.min(0).values
+    samples = rnd.uniform(key, (n_sample, m)).to(points.device) * (ref - f_min) + f_min
+    return hv_contrib(samples, points, hv_count(samples, points, strict=False), alpha)

@@ -18,13 +18,13 @@
   gde3  : GDE3 pop=4096 on DTLZ2 (m=3, d=500)              — 1×MI355X
   moead : MOEA/D pop=16384 on LSMOP1 (m=3, d=10000), Tchebycheff aggregation
 
-  --runs R (nsga2, gde3, ibea, spea2, nsga3, moead — MOEA/D then runs DTLZ2 with PBI): R independent seeds, the protocol of a multi-objective comparison (20–30 runs at
+  --runs R (nsga2, gde3, ibea, spea2, nsga3, hype, moead — MOEA/D then runs DTLZ2 with PBI): R independent seeds, the protocol of a multi-objective comparison (20–30 runs at
   pop 100–200).  Without --batched the R seeds run one after another, each its own workflow (and hipGraph);
   with --batched they are one BatchedRuns workflow, every launch of a generation advancing all R runs.
   Both modes start run r from split(fold_in(key, 1), R)[r], so they compute the same runs; ms_per_gen is the
   time of one generation of all R runs, and after the timed region every run's IGD is printed.
 
-python tools/bench_mo.py --algo nsga2|gde3|ibea|spea2|nsga3|moead [--pop 100 --dim 12] --runs 32 [--batched]
+python tools/bench_mo.py --algo nsga2|gde3|ibea|spea2|nsga3|hype|moead [--pop 100 --dim 12] --runs 32 [--batched]
 python tools/bench_mo.py --algo nsga2|nsga3|sra|ibea|spea2|bceibea|knea|m2m|rvea|rveaa|lmocso|bige|tdea|moead [--gens 20] [--warmup 3] [--no-graph]
 torchrun --nproc-per-node 8 --master-addr 127.0.0.1 tools/bench_mo.py --algo moead
 
@@ -49,15 +49,15 @@ import torch  # noqa: E402
 
 
 def build(args, dev):
-    from evoxmi.algorithms import GDE3, BCEIBEA, IBEA, LMOCSO, MOEAD, MOEADM2M, NSGA2, NSGA3, RVEA, SPEA2, SRA, TDEA, BiGE, KnEA, RVEAa
+    from evoxmi.algorithms import GDE3, BCEIBEA, IBEA, LMOCSO, HypE, MOEAD, MOEADM2M, NSGA2, NSGA3, RVEA, SPEA2, SRA, TDEA, BiGE, KnEA, RVEAa
     from evoxmi.problems.numerical import DTLZ2, LSMOP1
 
     m = 3
-    if args.algo in ("nsga2", "gde3", "nsga3", "sra", "ibea", "spea2", "bceibea", "knea", "m2m", "rvea", "rveaa", "lmocso", "bige", "tdea"):
+    if args.algo in ("nsga2", "gde3", "nsga3", "sra", "ibea", "spea2", "bceibea", "knea", "m2m", "rvea", "rveaa", "lmocso", "bige", "tdea", "hype"):
         d = args.dim or 500
         lb, ub = torch.zeros(d, device=dev), torch.ones(d, device=dev)
         algos = {"nsga2": NSGA2, "gde3": GDE3, "nsga3": NSGA3, "sra": SRA, "ibea": IBEA, "spea2": SPEA2, "bceibea": BCEIBEA, "knea": KnEA,
-                 "m2m": MOEADM2M, "rvea": RVEA, "rveaa": RVEAa, "bige": BiGE, "tdea": TDEA}
+                 "m2m": MOEADM2M, "rvea": RVEA, "rveaa": RVEAa, "bige": BiGE, "tdea": TDEA, "hype": HypE}
         if args.algo == "lmocso":  # its constructor takes n_objs first
             return LMOCSO(m, lb, ub, args.pop or 4096), DTLZ2(d=d, m=m)
         return algos[args.algo](lb, ub, m, args.pop or (4000 if args.algo == "m2m" else 4096)), DTLZ2(d=d, m=m)
@@ -124,7 +124,7 @@ def main():
     from evoxmi.workflows import StdWorkflow
 
     ap = argparse.ArgumentParser()
-    ap.add_argument("--algo", choices=["nsga2", "gde3", "nsga3", "sra", "ibea", "spea2", "bceibea", "knea", "m2m", "rvea", "rveaa", "lmocso", "bige", "tdea", "moead"], default="nsga2")
+    ap.add_argument("--algo", choices=["nsga2", "gde3", "nsga3", "sra", "ibea", "spea2", "bceibea", "knea", "m2m", "rvea", "rveaa", "lmocso", "bige", "tdea", "hype", "moead"], default="nsga2")
     ap.add_argument("--gpus", type=int, default=1, help="ranks (one per GPU); spawned here unless torchrun started them")
     ap.add_argument("--pop", type=int, default=0)
     ap.add_argument("--dim", type=int, default=0)
@@ -132,7 +132,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--cpu", action="store_true")
-    ap.add_argument("--runs", type=int, default=0, help="nsga2 / gde3 / ibea / spea2 / nsga3: this many independent seeds (one GPU)")
+    ap.add_argument("--runs", type=int, default=0, help="nsga2 / gde3 / ibea / spea2 / nsga3 / hype / moead: this many independent seeds (one GPU)")
     ap.add_argument("--batched", action="store_true", help="with --runs: all seeds as one BatchedRuns workflow")
     ap.add_argument("--force-dist", action="store_true", help="sharded protocol even on one rank")
     ap.add_argument("--simulate-rank", type=int, default=None,  # -1 (MOEA/D): the rank with the largest halo
@@ -142,8 +142,8 @@ def main():
     ap.add_argument("--link-gbps", type=float, default=None, help="--simulate-rank wire model: GB/s per xGMI link and direction")
     args = ap.parse_args()
     if args.runs or args.batched:
-        if args.algo not in ("nsga2", "gde3", "ibea", "spea2", "moead", "nsga3") or args.runs < 1 or args.gpus != 1 or args.simulate_rank is not None or args.force_dist:
-            ap.error("--runs R [--batched] needs R >= 1, --algo nsga2, gde3, ibea, spea2, moead or nsga3, and one rank")
+        if args.algo not in ("nsga2", "gde3", "ibea", "spea2", "moead", "nsga3", "hype") or args.runs < 1 or args.gpus != 1 or args.simulate_rank is not None or args.force_dist:
+            ap.error("--runs R [--batched] needs R >= 1, --algo nsga2, gde3, ibea, spea2, moead, nsga3 or hype, and one rank")
         return run_seeds(args, torch.device("cpu" if args.cpu else "cuda"))
     import torch.distributed as dist
     from evoxmi.parallel import init_distributed
