@@ -1796,6 +1796,33 @@ std::vector<at::Tensor> rvea_select(const at::Tensor& f, const c10::optional<at:
   return {next_ind, empty, arg, apd, gamma};
 }
 
+// rvea_select for B runs in one launch of rvea_small.hip: f (B, n, m), shift (B, m), v (B, nv, m), theta (B,) → next_ind (B, nv) int64,
+// empty (B, nv) bool, arg (B, n) int32, apd (B, n) and gamma (B, nv) float64, every run the words of rvea_select on its slices
+std::vector<at::Tensor> rvea_small_select(const at::Tensor& f, const at::Tensor& shift, double floor, const at::Tensor& v,
+                                          const at::Tensor& theta) {
+  const char* op = "rvea_small_select";
+  CHECK_DEV(f); CHECK_F32(f); CHECK_CONTIG(f); CHECK_DEV(v); CHECK_F32(v); CHECK_CONTIG(v);
+  CHECK_DEV(shift); CHECK_F32(shift); CHECK_CONTIG(shift); CHECK_DEV(theta); CHECK_F32(theta); CHECK_CONTIG(theta);
+  TORCH_CHECK(f.dim() == 3 && v.dim() == 3 && f.size(0) >= 1 && v.size(0) == f.size(0), op, ": f float32 (B, n, m), v float32 (B, nv, m)");
+  const int64_t B = f.size(0), n = f.size(1), nv = v.size(1), m = f.size(2);
+  TORCH_CHECK(shift.dim() == 2 && shift.size(0) == B && theta.dim() == 1 && theta.size(0) == B && theta.device() == f.device(), op,
+              ": shift float32 (B, m) and theta float32 (B,) on the device of f");
+  rvea_check(op, f.select(0, 0), shift.select(0, 0), v.select(0, 0));  // every run has the shape of the first
+  TORCH_CHECK(evx_rvea_small_ok(n, nv, m), op, ": needs n <= 4096 rows and nv <= 2048 (m <= 4), 1024 (m <= 8) or 512 (m <= 16) vectors per run, got n = ",
+              n, ", nv = ", nv, ", m = ", m);
+  c10::DeviceGuard g(f.device());
+  auto f64 = f.options().dtype(at::kDouble);
+  auto next_ind = at::empty({B, nv}, f.options().dtype(at::kLong));
+  auto empty = at::empty({B, nv}, f.options().dtype(at::kBool));
+  auto arg = at::empty({B, n}, f.options().dtype(at::kInt));
+  auto apd = at::empty({B, n}, f64);
+  auto gamma = at::empty({B, nv}, f64);
+  evx_rvea_small_select(f.data_ptr<float>(), shift.data_ptr<float>(), floor, v.data_ptr<float>(), theta.data_ptr<float>(), (int)B, (int)n,
+                        (int)nv, (int)m, next_ind.data_ptr<int64_t>(), empty.data_ptr<bool>(), arg.data_ptr<int>(), apd.data_ptr<double>(),
+                        gamma.data_ptr<double>(), cur_stream());
+  return {next_ind, empty, arg, apd, gamma};
+}
+
 // bi (n, 2) float32, then pr and cd (n,) float64 of bige_select.hip: BiGE's bi-goal estimate of the masked rows of fit (n, m);
 // r is one float32 device word
 std::vector<at::Tensor> bige_estimate(const at::Tensor& fit, const at::Tensor& mask, const at::Tensor& r) {
@@ -2264,6 +2291,7 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("knea_select(Tensor obj, Tensor rank, int N, Tensor r, Tensor t, float knee_rate) -> Tensor[]");
   m.def("rvea_cos_best(Tensor A, Tensor? shift, float? floor, Tensor B, bool clamp, bool self_zero) -> Tensor[]");
   m.def("rvea_select(Tensor f, Tensor? shift, float? floor, Tensor v, Tensor theta) -> Tensor[]");
+  m.def("rvea_small_select(Tensor f, Tensor shift, float floor, Tensor v, Tensor theta) -> Tensor[]");
   m.def("bige_estimate(Tensor fit, Tensor mask, Tensor r) -> Tensor[]");
   m.def("hv_exact(Tensor pT, Tensor vals, Tensor idx) -> Tensor");
   m.def("hv_contributions(Tensor pT, Tensor vals, Tensor idx) -> Tensor");
@@ -2374,6 +2402,7 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("knea_select", &knea_select);
   m.impl("rvea_cos_best", &rvea_cos_best);
   m.impl("rvea_select", &rvea_select);
+  m.impl("rvea_small_select", &rvea_small_select);
   m.impl("bige_estimate", &bige_estimate);
   m.impl("hv_exact", &hv_exact);
   m.impl("hv_contributions", &hv_contributions);

@@ -271,6 +271,13 @@ void evx_rvea_cos_best(const float* A, const float* shift, int has_floor, double
                        hipStream_t s);
 void evx_rvea_pick(const int* arg, const double* apd, int n, int nv, const uint64_t* key, int* pick, int64_t* next_ind, bool* empty,
                    hipStream_t s);
+// rvea_small.hip: the same selection for B runs in one launch, a workgroup per run with the run's normalised vectors in LDS and no
+// scratch.  f (B, n, m), shift (B, m), v (B, nv, m), theta (B,) → next_ind, empty (B, nv), arg, apd (B, n), gamma (B, nv), run by run
+// the words of the three launchers above.  evx_rvea_small_ok: the shapes it takes (m ≤ 16, n ≤ 4096, nv · MC ≤ 8192 for MC = 4, 8, 16
+// the padded m)
+bool evx_rvea_small_ok(int64_t n, int64_t nv, int64_t m);
+void evx_rvea_small_select(const float* f, const float* shift, double floor_v, const float* v, const float* theta, int B, int n, int nv, int m,
+                           int64_t* next_ind, bool* empty, int* arg, double* apd, double* gamma, hipStream_t s);
 // bige_select.hip: BiGE's bi-goal estimate (m ≤ 16; the contract is in evoxmi/ops/bige.py).  Three launches: the float32
 // column extremes of the masked rows into fmin, fmax (m each), the normalised rows into the float64 scratch x (m, n) and
 // their sums into prs (n), then bi (n, 2) float32 with its float64 parts pr and cd (n each); r is one float32 device

@@ -21,32 +21,21 @@
 #include <stdint.h>
 
 #include "evoxmi_launchers.h"
+#include "evoxmi_rvea.h"
 
 namespace {
+
+using namespace evx;  // the arithmetic both this file and rvea_small.hip use: evoxmi_rvea.h
 
 constexpr int RV_THREADS = 1024;
 constexpr int RV_WAVES = RV_THREADS / 64;
 constexpr int RV_TILE_WORDS = 4096;  // float64 words of b̂ per LDS tile
-constexpr int RV_NO_ROW = INT_MAX;
-
-// the bits of a double as an unsigned word whose order is the order of the values; a non-finite value ranks as +inf
-__device__ inline unsigned long long rv_ordered(double x) {
-  if (!(fabs(x) <= 1.7976931348623157e308)) x = INFINITY;
-  x = x + 0.0;  // −0 → +0
-  unsigned long long u = (unsigned long long)__double_as_longlong(x);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
 
 __global__ void rvea_prepare_kernel(const float* __restrict__ B, int k, int m, double* __restrict__ bn, unsigned long long* __restrict__ key,
                                     int* __restrict__ pick, int nkey) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j < k) {
-    double s = 0.0;
-    for (int t = 0; t < m; ++t) {
-      const double b = (double)B[(size_t)j * m + t];
-      s = t == 0 ? b * b : s + b * b;
-    }
-    const double nrm = sqrt(s);
+    const double nrm = rv_vector_norm(B + (size_t)j * m, m);
     for (int t = 0; t < m; ++t) bn[(size_t)t * k + j] = (double)B[(size_t)j * m + t] / nrm;
   }
   if (key != nullptr && j < nkey) {
@@ -72,24 +61,7 @@ __global__ void __launch_bounds__(RV_THREADS)
   bool nan_row = false;
 #pragma unroll
   for (int t = 0; t < MC; ++t) a[t] = 0.0;
-  if (live) {
-    double s = 0.0;
-#pragma unroll
-    for (int t = 0; t < MC; ++t)
-      if (t < m) {
-        const float x = A[(size_t)i * m + t];
-        nan_row |= x != x;
-        double d = (double)x;
-        if (shift != nullptr) d = d - (double)shift[t];
-        if (has_floor && d < floor_v) d = floor_v;  // a NaN stays
-        a[t] = d;
-        s = t == 0 ? d * d : s + d * d;
-      }
-    nrm = sqrt(s);
-#pragma unroll
-    for (int t = 0; t < MC; ++t)
-      if (t < m) a[t] = a[t] / nrm;
-  }
+  if (live) nrm = rv_load_row<MC>(A + (size_t)i * m, shift, has_floor, floor_v, m, a, nan_row);
   const bool scan = live && !nan_row;
   double bst = -INFINITY;
   int arg = RV_NO_ROW;
@@ -103,17 +75,8 @@ __global__ void __launch_bounds__(RV_THREADS)
     __syncthreads();
     if (scan) {
       for (int jj = lane; jj < w; jj += 64) {
-        double c = 0.0;
-#pragma unroll
-        for (int t = 0; t < MC; ++t)
-          if (t < m) {
-            const double p = a[t] * tile[t * TJ + jj];
-            c = t == 0 ? p : c + p;
-          }
-        if (c != c) c = -INFINITY;
-        else if (clamp) c = c < 0.0 ? 0.0 : (c > 1.0 ? 1.0 : c);
         const int j = j0 + jj;
-        if (self_zero && j == i) c = 0.0;
+        const double c = rv_cosine<MC>(a, tile + jj, TJ, m, clamp, self_zero && j == i);
         if (c > bst) {
           bst = c;
           arg = j;
@@ -122,22 +85,9 @@ __global__ void __launch_bounds__(RV_THREADS)
     }
   }
   if (!live) return;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double ob = __shfl_xor(bst, off);
-    const int oa = __shfl_xor(arg, off);
-    if (ob > bst || (ob == bst && oa < arg)) {
-      bst = ob;
-      arg = oa;
-    }
-  }
+  rv_wave_best(bst, arg);
   if (lane != 0) return;
-  if (nan_row) {
-    bst = self_zero ? 0.0 : -INFINITY;
-    arg = -1;
-  } else if (arg == RV_NO_ROW) {
-    arg = 0;  // every entry −inf
-  }
+  rv_settle(nan_row, self_zero, bst, arg);
   best_out[i] = bst;
   arg_out[i] = arg;
   if (mode == 1) {
@@ -145,8 +95,7 @@ __global__ void __launch_bounds__(RV_THREADS)
   } else if (mode == 2) {
     double apd = INFINITY;
     if (arg >= 0) {
-      const double angle = acos(bst);
-      apd = (1.0 + (((double)m * (double)theta[0]) * angle) / gamma[arg]) * nrm;
+      apd = rv_apd(m, theta[0], bst, gamma[arg], nrm);
       atomicMin(&key[arg], rv_ordered(apd));
     }
     aux[i] = apd;

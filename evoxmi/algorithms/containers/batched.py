@@ -53,9 +53,16 @@ HIP device the two launches of ``hype_fitness.hip`` with the run on ``grid.y`` (
 to the two-pass path it replaces, so the solo trajectory did not move.  On the CPU its non-dominated sort runs run by run inside a
 Python-registered op (``evoxmi.ops.nds.rank_under_vmap``).
 
-Covered multi-objective algorithms: NSGA-II, GDE3, IBEA, SPEA2, MOEA/D, NSGA-III, HypE.  The others are not, and an uncovered one is not
-guaranteed to raise.  Most raise from ``vmap`` (their selections read the host or loop on data), but RVEA runs and its
-runs differ from solo runs: do not rely on ``BatchedRuns`` over an algorithm that is not listed here.
+RVEA batches (``tests/test_batched_rvea.py``, ``tests/test_batched_rvea_gpu.py``): on a HIP device its APD selection, five launches
+for one run, is ONE launch of ``rvea_small.hip`` for all of them, a workgroup per run that keeps the run's normalised reference
+vectors, γ and the per-vector minima in LDS (no scratch, no global atomics), each run with its own adapted vectors and θ.  It gives
+every run the words of the solo kernels, for merged populations of at most 4096 rows and 2048, 1024 or 512 reference vectors at up to
+4, 8 or 16 objectives per run (``NotImplementedError`` above); the rest of its tell is torch ops that ``vmap`` batches itself.
+RVEA*, LMOCSO and θ-DEA, which share the solo kernels, are not covered: their ``rvea_cos_best`` raises under ``vmap``.
+
+Covered multi-objective algorithms: NSGA-II, GDE3, IBEA, SPEA2, MOEA/D, NSGA-III, HypE, RVEA.  The others are not, and an uncovered
+one is not guaranteed to raise, though most do, from ``vmap`` (their selections read the host or loop on data) or from an op's rule:
+do not rely on ``BatchedRuns`` over an algorithm that is not listed here.
 """
 from __future__ import annotations
 

@@ -29,7 +29,11 @@ per run).  Each rule moves the run axis to the front and calls the op's batched 
   rank, group, group_dist (B, n), last_rank (B,), keys (B, 2) → one workgroup per run (``nsga3_select.hip``);
 * ``hype_fitness``: points (B, n, m), ref (B, m), keys (B, 2) → grid.y = run in both kernels (``hype_fitness.hip``; n ≤ 2048, m ≤ 16,
   n_sample ≤ 2^20 per run), α shared by the runs.  ``hv_count`` and ``hv_contrib`` have no batched form: their rules pass unbatched
-  calls through and raise on batched operands (``tests/test_hype_fitness_gpu.py``).
+  calls through and raise on batched operands (``tests/test_hype_fitness_gpu.py``);
+* ``rvea_select``: f (B, n, m), shift (B, m), v (B, nv, m), θ (B,) → ``rvea_small_select``, one workgroup per run that keeps the run's
+  normalised vectors in LDS (``rvea_small.hip``; n ≤ 4096 and nv ≤ 2048, 1024 or 512 for m ≤ 4, 8 or 16 per run); an unbatched
+  operand is broadcast.  Every output of run r is the 2-D op's on that run, bit for bit (``tests/test_batched_rvea_gpu.py``).
+  ``rvea_cos_best`` has no batched form: its rule passes unbatched calls through and raises on batched operands.
 
 Each run's words/trials are bit-identical to the single-run op with that run's key
 (``tests/test_batched_runs.py``), each run's sorted keys and indices to the op applied row by row
@@ -291,6 +295,28 @@ def _hv_contrib(info, in_dims, S, P, count, alpha):
     return _ext.ops().hv_contrib(S, P, count, alpha), None
 
 
+def _rvea_select(info, in_dims, f, shift, floor, v, theta):
+    from .rvea import check_small_caps
+
+    B, what = info.batch_size, "rvea_select vmap rule"
+    if all(d is None for d in in_dims):
+        return list(_ext.ops().rvea_select(f, shift, floor, v, theta)), [None] * 5
+    if shift is None or floor is None:
+        raise NotImplementedError(f"{what}: batched runs take a shift and a floor (the APD selection passes both)")
+    fb = _runs_of(f, in_dims[0], B, 2, what)
+    vb = _runs_of(v, in_dims[3], B, 2, what)
+    check_small_caps(fb.shape[1], vb.shape[1], fb.shape[2], what)
+    out = _ext.ops().rvea_small_select(fb, _runs_of(shift, in_dims[1], B, 1, what), floor, vb, _front(theta, in_dims[4], B).reshape(B))
+    return list(out), [0] * 5
+
+
+def _rvea_cos_best(info, in_dims, A, shift, floor, B, clamp, self_zero):
+    if any(d is not None for d in in_dims):
+        raise NotImplementedError("rvea_cos_best vmap rule: no batched form (RVEA's batched runs go through rvea_select, within its caps; "
+                                  "RVEA*, LMOCSO and θ-DEA are not covered)")
+    return list(_ext.ops().rvea_cos_best(A, shift, floor, B, clamp, self_zero)), [None, None]
+
+
 def register():
     """Install the rules (idempotent).  Without the compiled extension there is nothing to
     batch: CPU tensors never reach the HIP ops, and a device op raises on its own."""
@@ -303,6 +329,7 @@ def register():
                      ("spea2_truncate", _spea2_truncate), ("cma_small_ask", _cma_small_ask), ("cma_small_tell", _cma_small_tell),
                      ("moead_small_ask", _moead_small_ask), ("moead_small_tell", _moead_small_tell),
                      ("nsga3_associate", _nsga3_associate), ("nsga3_niche_select", _nsga3_niche_select),
-                     ("hype_fitness", _hype_fitness), ("hv_count", _hv_count), ("hv_contrib", _hv_contrib)):
+                     ("hype_fitness", _hype_fitness), ("hv_count", _hv_count), ("hv_contrib", _hv_contrib),
+                     ("rvea_select", _rvea_select), ("rvea_cos_best", _rvea_cos_best)):
         torch.library.register_vmap(f"evoxmi::{name}", fn)
     _REGISTERED = True

@@ -84,6 +84,7 @@ def _run(cmd):
 # knea_select.hip: its contract is float64 arithmetic in a stated operation order with no FMA, so a
 # host implementation of the same operations reproduces its keys and box tests bit for bit
 # rvea_select.hip: the same kind of contract: its cosines are symmetric bit for bit and a host implementation reproduces them
+# rvea_small.hip: the batched form of rvea_select.hip; its runs must equal that file's launches bit for bit (shared arithmetic: evoxmi_rvea.h)
 # bige_select.hip, tdea_select.hip: the same kind of contract: a host implementation reproduces BiGE's proximity and θ-DEA's
 # penalised distance bit for bit
 # nsga3_assoc.hip: the same kind of contract (NSGA-III's nadir and perpendicular distances), and the solo and the batched call
@@ -99,7 +100,7 @@ def _run(cmd):
 # switched off for this file alone the other product is fused and offspring differ in the last bit
 FILE_FLAGS = {"cma_small.hip": ["-ffp-contract=fast-honor-pragmas", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "eigh_sbr.hip": ["-fno-slp-vectorize"], "mo_geom.hip": ["-ffp-contract=fast-honor-pragmas"],
-              "knea_select.hip": ["-ffp-contract=off"], "rvea_select.hip": ["-ffp-contract=off"],
+              "knea_select.hip": ["-ffp-contract=off"], "rvea_select.hip": ["-ffp-contract=off"], "rvea_small.hip": ["-ffp-contract=off"],
               "bige_select.hip": ["-ffp-contract=off"], "tdea_select.hip": ["-ffp-contract=off"],
               "nsga3_assoc.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "hv_exact.hip": ["-ffp-contract=off"], "hype_fitness.hip": ["-ffp-contract=off"],

@@ -34,6 +34,11 @@ That holds for finite objectives plus whole-NaN padding rows, and reference vect
 pairwise not parallel (γ > 0).  A row with ±∞, a zero or non-finite vector, or γ = 0 get only this: the launches end,
 ``next_ind`` lies in [0, n) and ``arg`` in [−1, k).  (The torch path lets a NaN win an ``argmin`` there.)
 
+``select`` on ``f`` (B, n, m), and ``rvea_select`` under ``vmap`` (``evoxmi/ops/batching.py``), select for B independent runs in
+one launch of ``rvea_small.hip``: a workgroup per run with the run's b̂, γ and the pick's words in LDS, the same operations
+(``csrc/include/evoxmi_rvea.h`` holds them for both files), so every run gets the words of the launches above.  Its caps per run
+are ``SMALL_N_CAP`` rows and ``SMALL_BN_WORDS`` float64 words of b̂; above them it raises, it does not go run by run.
+
 The torch path is the expressions ``ref_vec_guided``, ``rv_regeneration`` and ``batch_truncation`` held before, in
 float32; it is the CPU path, the path above the caps, and the oracle of the float32 behaviour."""
 from __future__ import annotations
@@ -45,6 +50,20 @@ from . import _ext
 
 M_CAP = 16  # rvea_select.hip: â stays in registers
 N_CAP = 32768  # rows and vectors; not structural: it bounds the scratch (RVEA* at pop 8192 merges n = 24576 rows)
+# rvea_small.hip, a workgroup per run (``select`` on (B, n, m), and ``rvea_select`` under ``vmap``): a run's b̂ stays in LDS
+SMALL_N_CAP = 4096  # rows per run
+SMALL_BN_WORDS = 8192  # nv · MC float64 words per run, MC = 4, 8 or 16 the padded m: nv ≤ 2048 (m ≤ 4), 1024 (m ≤ 8), 512 (m ≤ 16)
+
+
+def small_ok(n: int, nv: int, m: int) -> bool:
+    """Whether runs of n rows against nv vectors of m objectives fit the one-workgroup-per-run kernel."""
+    return 1 <= m <= M_CAP and 1 <= n <= SMALL_N_CAP and 1 <= nv and nv * (4 if m <= 4 else 8 if m <= 8 else 16) <= SMALL_BN_WORDS
+
+
+def check_small_caps(n: int, nv: int, m: int, what: str):
+    if not small_ok(n, nv, m):
+        raise NotImplementedError(f"{what}: batched runs need m <= {M_CAP}, n <= {SMALL_N_CAP} rows and nv <= 2048 (m <= 4), 1024 (m <= 8) "
+                                  f"or 512 (m <= 16) vectors per run, got n = {n}, nv = {nv}, m = {m}")
 
 
 def on_device(n: int, k: int, m: int, device) -> bool:
@@ -101,12 +120,37 @@ def _select_torch(f, v, theta):
     return next_ind, empty
 
 
+def _select_runs(f, v, theta, return_info):
+    B, n, m = f.shape
+    if v.dim() == 2:
+        v = v.unsqueeze(0).expand(B, -1, -1)
+    theta = torch.as_tensor(theta, dtype=torch.float32).to(device=f.device, dtype=torch.float32).expand(B)
+    if f.device.type == "cuda":
+        if f.dtype != torch.float32 or v.dtype != torch.float32:
+            raise NotImplementedError("ops.rvea.select: batched runs on a device need float32 objectives and vectors")
+        check_small_caps(n, v.shape[1], m, "ops.rvea.select")
+        shift = torch.nan_to_num(f, nan=float("inf")).min(1).values  # exact in torch
+        next_ind, empty, arg, apd, gamma = _ext.ops().rvea_small_select(f.contiguous(), shift, 1e-32, v.contiguous(), theta.contiguous())
+        return (next_ind, empty, arg.to(torch.int64), apd, gamma) if return_info else (next_ind, empty)
+    if return_info:
+        raise ValueError("return_info is the kernels' only")
+    runs = [_select_torch(f[r], v[r], theta[r]) for r in range(B)]
+    return torch.stack([r[0] for r in runs]), torch.stack([r[1] for r in runs])
+
+
 def select(f: torch.Tensor, v: torch.Tensor, theta, return_info: bool = False):
     """``(next_ind, empty)``: RVEA's APD selection of the rows ``f`` (n, m), NaN rows being padding, on the reference
     vectors ``v`` (nv, m): ``next_ind`` (nv,) int64 the row each vector keeps and ``empty`` (nv,) bool the vectors
     without a member.  ``theta`` is a Python float or a 0-dim tensor.  On a HIP device within the caps five launches of
     ``rvea_select.hip`` that read nothing on the host and build no (n, nv) array (``return_info`` adds ``arg``, ``apd`` and
-    ``gamma``); elsewhere the dense float32 expressions."""
+    ``gamma``); elsewhere the dense float32 expressions.
+
+    ``f`` (B, n, m) selects for B independent runs: ``v`` is (B, nv, m) or one (nv, m) for all runs, ``theta`` a float, a
+    0-dim tensor or (B,), and every result gains a leading run axis.  On a HIP device that is the column minimum and ONE
+    launch of ``rvea_small.hip``, a workgroup per run, whose words are those of the 2-D call on each run; runs above its caps
+    (``SMALL_N_CAP``, ``SMALL_BN_WORDS``) raise ``NotImplementedError``.  On the CPU the torch path runs run by run."""
+    if f.dim() == 3:
+        return _select_runs(f, v, theta, return_info)
     if _kernel_path(f, v):
         if not isinstance(theta, torch.Tensor):
             theta = torch.tensor(float(theta), dtype=torch.float32)
