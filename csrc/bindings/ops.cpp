@@ -1936,6 +1936,33 @@ std::vector<at::Tensor> sra_indicators(const at::Tensor& obj) {
   return {I1, I2};
 }
 
+// idx (n,) int64 best first, then I1 and I2 (n,) float32: SRA's selection of one population, exactly the two launches of
+// sra_indicators and sra_rank
+std::vector<at::Tensor> sra_select(const at::Tensor& obj, const at::Tensor& u, const at::Tensor& pc) {
+  auto ind = sra_indicators(obj);
+  return {sra_rank(ind[0], ind[1], u, pc), ind[0], ind[1]};
+}
+
+// sra_select for B runs in one launch of sra_small.hip: obj (B, n, m), u (B, ≥ n − 1), pc (B,) → idx (B, n) int64, I1 and I2 (B, n)
+// float32, every run the words of sra_select on its slices
+std::vector<at::Tensor> sra_small_select(const at::Tensor& obj, const at::Tensor& u, const at::Tensor& pc) {
+  const char* op = "sra_small_select";
+  CHECK_DEV(obj); CHECK_F32(obj); CHECK_CONTIG(obj); CHECK_DEV(u); CHECK_F32(u); CHECK_CONTIG(u); CHECK_DEV(pc); CHECK_F32(pc); CHECK_CONTIG(pc);
+  TORCH_CHECK(obj.dim() == 3 && obj.size(0) >= 1, op, ": obj float32 (B, n, m)");
+  const int64_t B = obj.size(0), n = obj.size(1), m = obj.size(2);
+  TORCH_CHECK(evx_sra_small_ok(n, m), op, ": needs 1 <= n <= 2048 rows at m <= 8 objectives or n <= 1024 at m <= 16 per run, got n = ", n,
+              ", m = ", m);
+  TORCH_CHECK(u.dim() == 2 && u.size(0) == B && u.size(1) >= n - 1, op, ": u float32 (B, at least n - 1)");
+  TORCH_CHECK(pc.dim() == 1 && pc.size(0) == B, op, ": pc float32 (B,)");
+  TORCH_CHECK(u.device() == obj.device() && pc.device() == obj.device(), op, ": one device");
+  c10::DeviceGuard g(obj.device());
+  auto idx = at::empty({B, n}, obj.options().dtype(at::kLong));
+  auto I1 = at::empty({B, n}, obj.options()), I2 = at::empty({B, n}, obj.options());
+  evx_sra_small_select(obj.data_ptr<float>(), u.data_ptr<float>(), (int)u.size(1), pc.data_ptr<float>(), (int)B, (int)n, (int)m,
+                       idx.data_ptr<int64_t>(), I1.data_ptr<float>(), I2.data_ptr<float>(), cur_stream());
+  return {idx, I1, I2};
+}
+
 // ibea_select.hip and spea2_select.hip: obj (n, m) is one population, (B, n, m) B independent runs in one launch; the per-row operands
 // are then (B, n) and every output gains the leading B
 struct RunShape {
@@ -2298,6 +2325,8 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("tdea_theta_rank(Tensor obj, Tensor w, Tensor theta, Tensor mask) -> Tensor[]");
   m.def("sra_rank(Tensor I1, Tensor I2, Tensor u, Tensor pc) -> Tensor");
   m.def("sra_indicators(Tensor obj) -> Tensor[]");
+  m.def("sra_select(Tensor obj, Tensor u, Tensor pc) -> Tensor[]");
+  m.def("sra_small_select(Tensor obj, Tensor u, Tensor pc) -> Tensor[]");
   m.def("ibea_fitness(Tensor obj_norm, float kappa) -> Tensor[]");
   m.def("ibea_truncate(Tensor obj_norm, Tensor f, Tensor C, float kappa, int n_remove, int n_keep) -> Tensor[]");
   m.def("spea2_fitness(Tensor obj) -> Tensor[]");
@@ -2409,6 +2438,8 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("tdea_theta_rank", &tdea_theta_rank);
   m.impl("sra_rank", &sra_rank);
   m.impl("sra_indicators", &sra_indicators);
+  m.impl("sra_select", &sra_select);
+  m.impl("sra_small_select", &sra_small_select);
   m.impl("ibea_fitness", &ibea_fitness);
   m.impl("ibea_truncate", &ibea_truncate);
   m.impl("spea2_fitness", &spea2_fitness);

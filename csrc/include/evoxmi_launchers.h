@@ -305,6 +305,12 @@ int evx_sra_rank_max_n();
 int evx_sra_indicators_max_m();
 void evx_sra_rank(const float* I1, const float* I2, const float* u, const float* pc, int n, int64_t* rank, hipStream_t s);
 void evx_sra_indicators(const float* obj, int n, int m, float* I1, float* I2, hipStream_t s);
+// sra_small.hip: both steps for B runs in one launch, a workgroup per run that keeps the run's objectives, indicators and sort items
+// in LDS and registers: obj (B, n, m), u (B, u_stride) with u_stride ≥ n − 1, pc (B,) → idx (B, n) best first, I1 and I2 (B, n), every
+// run the words of the two launchers above.  evx_sra_small_ok: the shapes it takes (n ≤ 2048 at m ≤ 8, n ≤ 1024 at m ≤ 16)
+bool evx_sra_small_ok(int64_t n, int64_t m);
+void evx_sra_small_select(const float* obj, const float* u, int u_stride, const float* pc, int B, int n, int m, int64_t* idx, float* I1,
+                          float* I2, hipStream_t s);
 // ibea_select.hip and spea2_select.hip take B independent runs in one launch: every array gains a leading run axis (obj (B, n, m),
 // per-row arrays (B, n), …), the fitness kernels put the run on grid.y and the removal kernels run one workgroup per run.  B = 1 is
 // a single population.

@@ -38,30 +38,19 @@
 //   sra_indicators     62    58    0        17664
 // No spill; the ranking's LDS is the two edge buffers (2 × 2 × 1024 items of 12 B) of the CU's
 // 160 KiB.
-#include "evoxmi_mo.h"
+#include "evoxmi_sra.h"
 
 namespace {
+
+using evx::SrItem;
+using evx::sr_cswap;
 
 constexpr int SR_THREADS = 1024;
 constexpr int SR_MAX = 8192;  // cap on n
 
-struct SrItem {
-  float a, b;
-  int id;
-};
-
 struct SrEdges {
   SrItem first[SR_THREADS], last[SR_THREADS];
 };
-
-__device__ __forceinline__ void sr_cswap(bool active, bool by_a, SrItem& x, SrItem& y) {
-  const float kx = by_a ? x.a : x.b, ky = by_a ? y.a : y.b;
-  if (active && kx < ky) {
-    const SrItem t = x;
-    x = y;
-    y = t;
-  }
-}
 
 template <int IT>
 __global__ void __launch_bounds__(SR_THREADS) sra_rank_kernel(const float* __restrict__ I1, const float* __restrict__ I2,
@@ -84,13 +73,12 @@ __global__ void __launch_bounds__(SR_THREADS) sra_rank_kernel(const float* __res
   }
   const bool sel_left = r > 0 && base - 1 < n - 1 && u[base - 1] < pc;  // the selector of position base − 1
 
-  const int S = (n + 1) / 2;
-  const int T = (n - 1) + 2 * (S - 1);  // n = 1: 0 steps
+  const int lag = evx::sr_lag(n), T = evx::sr_steps(n, lag);
   // positions this thread takes part in: base − 1 (left edge) … base + IT − 1 (right edge)
   for (int t = 0; t < T; t += 2) {
     // even step t: comparators at even positions, all inside the thread
     {
-      const int lo = max(0, t - 2 * (S - 1)), hi = min(t, n - 2);
+      const int lo = evx::sr_lo(t, lag), hi = evx::sr_hi(t, n);
 #pragma unroll
       for (int i = 0; i < IT; i += 2) {
         const int j = base + i;
@@ -100,7 +88,7 @@ __global__ void __launch_bounds__(SR_THREADS) sra_rank_kernel(const float* __res
     if (t + 1 >= T) break;  // uniform over the block
     // odd step t + 1: inner comparators at odd positions, and the two edges through LDS
     {
-      const int lo = max(0, t + 1 - 2 * (S - 1)), hi = min(t + 1, n - 2);
+      const int lo = evx::sr_lo(t + 1, lag), hi = evx::sr_hi(t + 1, n);
       SrEdges& e = edges[(t >> 1) & 1];
       const int jl = base - 1, jr = base + IT - 1;
       const bool left = r > 0 && jl >= lo && jl <= hi, right = r + 1 < SR_THREADS && jr >= lo && jr <= hi;
@@ -134,9 +122,6 @@ constexpr int SI_THREADS = 64 * SI_WAVES;
 constexpr int SI_TILE = 256;          // rows q per LDS tile
 constexpr int SI_MAX_M = 16;
 
-using evx::nan_max;
-using evx::nan_min;
-
 __global__ void __launch_bounds__(SI_THREADS) sra_indicators_kernel(const float* __restrict__ obj, int n, int m, float* __restrict__ I1,
                                                                      float* __restrict__ I2) {
   __shared__ float qs[SI_TILE * (SI_MAX_M + 1)];
@@ -155,25 +140,11 @@ __global__ void __launch_bounds__(SI_THREADS) sra_indicators_kernel(const float*
     if (p < n) {
       for (int ql = lane; ql < rows; ql += 64) {
         const float* oq = qs + ql * ms;
-        float mx = oq[0] - ps[wave][0];
-        float c = mx < 0.f ? 0.f : mx;
-        float d2 = c * c;
-        for (int k = 1; k < m; ++k) {
-          const float d = oq[k] - ps[wave][k];
-          mx = nan_max(mx, d);
-          c = d < 0.f ? 0.f : d;
-          d2 += c * c;
-        }
-        sum += expf(-mx / 0.05f);
-        if (q0 + ql != p) mn = nan_min(mn, d2);  // sqrtf is monotone and keeps NaN: the root is taken once, below
+        EVX_SI_PAIR(oq, ps[wave], m, q0 + ql != p, sum, mn)
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {  // sum and min in one tree: as evx::wave_sum and wave_nan_min the code length changes (3516 to 3488 B)
-    sum += __shfl_xor(sum, o, 64);
-    mn = nan_min(mn, __shfl_xor(mn, o, 64));
-  }
+  EVX_SI_TREE(sum, mn)
   if (lane == 0 && p < n) {
     I1[p] = 1.f - sum;
     I2[p] = sqrtf(mn);

@@ -60,7 +60,13 @@ every run the words of the solo kernels, for merged populations of at most 4096 
 4, 8 or 16 objectives per run (``NotImplementedError`` above); the rest of its tell is torch ops that ``vmap`` batches itself.
 RVEA*, LMOCSO and θ-DEA, which share the solo kernels, are not covered: their ``rvea_cos_best`` raises under ``vmap``.
 
-Covered multi-objective algorithms: NSGA-II, GDE3, IBEA, SPEA2, MOEA/D, NSGA-III, HypE, RVEA.  The others are not, and an uncovered
+SRA batches (``tests/test_batched_sra.py``, ``tests/test_batched_sra_gpu.py``): on a HIP device its selection, two launches for one
+run with the ranking on a single compute unit, is ONE launch of ``sra_small.hip`` for all runs, a workgroup per run that forms both
+indicators from the run's rows in LDS and ranks them without writing them to global memory in between, each run with its own pc.  It
+gives every run the words of the solo kernels, for merged populations of at most 2048 rows at up to 8 objectives and 1024 at up to 16
+(``NotImplementedError`` above).  On the CPU the selection runs run by run inside a Python-registered op (``evoxmi.ops.sra.select_run``).
+
+Covered multi-objective algorithms: NSGA-II, GDE3, IBEA, SPEA2, MOEA/D, NSGA-III, HypE, RVEA, SRA.  The others are not, and an uncovered
 one is not guaranteed to raise, though most do, from ``vmap`` (their selections read the host or loop on data) or from an op's rule:
 do not rely on ``BatchedRuns`` over an algorithm that is not listed here.
 """

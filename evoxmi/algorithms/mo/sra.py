@@ -12,6 +12,10 @@ in one workgroup (``sra_select.hip``); pc stays a device word and nothing is rea
 host, so a whole generation is captured into one hipGraph (``StdWorkflow(..., graph=True)``).
 On the CPU, and above those caps, the indicators are the dense torch expressions and the sort
 is the sequential host op ``evoxmi::stochastic_ranking``; those sizes stay eager-only.
+
+Under ``BatchedRuns`` the device selection of all runs is ONE launch of ``sra_small.hip``, a workgroup per run (merged populations
+of at most 2048 rows at up to 8 objectives, 1024 at up to 16; ``NotImplementedError`` above); on the CPU the runs' selections
+go run by run inside a Python-registered op (``evoxmi.ops.sra.select_run``).
 """
 from __future__ import annotations
 
@@ -40,13 +44,17 @@ class SRA(MOAlgorithm):
         merged_fit = torch.cat([state.fitness, fitness], 0)
         key, k_pc, k_env = rnd.split(state.key, 3)
         n, m = merged_fit.shape
+        u = rnd.uniform(k_env, (n - 1,))
         if sra_ops.on_device(n, m, merged_fit.device):
             # the value the host path hands to the op (a double product, cast to float), as a device word
             pc = (rnd.uniform(k_pc, ()).double() * 0.2 + 0.4).float()
-            I1, I2 = sra_ops.indicators(merged_fit)
+            idx = sra_ops.select(merged_fit, u, pc)[: self.pop_size]
+        elif torch._C._functorch.is_batchedtensor(merged_fit):  # a run of BatchedRuns
+            if merged_fit.is_cuda:
+                sra_ops.check_small_caps(n, m, "SRA under BatchedRuns")  # above on_device's caps there is no batched device form
+            idx = sra_ops.select_run(merged_fit, u, rnd.uniform(k_pc, ()))[: self.pop_size]
         else:
             pc = float(rnd.uniform(k_pc, ())) * 0.2 + 0.4
             I1, I2 = sra_ops.indicators_dense(merged_fit)
-        u = rnd.uniform(k_env, (n - 1,))
-        idx = sra_ops.stochastic_rank(I1, I2, u, pc)[: self.pop_size]
+            idx = sra_ops.stochastic_rank(I1, I2, u, pc)[: self.pop_size]
         return state.update(population=merged_pop[idx], fitness=merged_fit[idx], key=key)

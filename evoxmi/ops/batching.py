@@ -33,7 +33,12 @@ per run).  Each rule moves the run axis to the front and calls the op's batched 
 * ``rvea_select``: f (B, n, m), shift (B, m), v (B, nv, m), θ (B,) → ``rvea_small_select``, one workgroup per run that keeps the run's
   normalised vectors in LDS (``rvea_small.hip``; n ≤ 4096 and nv ≤ 2048, 1024 or 512 for m ≤ 4, 8 or 16 per run); an unbatched
   operand is broadcast.  Every output of run r is the 2-D op's on that run, bit for bit (``tests/test_batched_rvea_gpu.py``).
-  ``rvea_cos_best`` has no batched form: its rule passes unbatched calls through and raises on batched operands.
+  ``rvea_cos_best`` has no batched form: its rule passes unbatched calls through and raises on batched operands.;
+* ``sra_select``: obj (B, n, m), u (B, n − 1), pc (B,) → ``sra_small_select``, one workgroup per run that forms both indicators and
+  ranks the rows without writing the indicators to global memory in between (``sra_small.hip``; n ≤ 2048 at m ≤ 8, n ≤ 1024 at
+  m ≤ 16 per run); an unbatched operand is broadcast.  Every output of run r is the 2-D op's on that run, bit for bit
+  (``tests/test_batched_sra_gpu.py``).  ``sra_indicators`` and ``sra_rank`` have no batched form: their rules pass unbatched calls
+  through and raise on batched operands.
 
 Each run's words/trials are bit-identical to the single-run op with that run's key
 (``tests/test_batched_runs.py``), each run's sorted keys and indices to the op applied row by row
@@ -317,6 +322,30 @@ def _rvea_cos_best(info, in_dims, A, shift, floor, B, clamp, self_zero):
     return list(_ext.ops().rvea_cos_best(A, shift, floor, B, clamp, self_zero)), [None, None]
 
 
+def _sra_select(info, in_dims, obj, u, pc):
+    from .sra import check_small_caps
+
+    B, what = info.batch_size, "sra_select vmap rule"
+    if all(d is None for d in in_dims):
+        return list(_ext.ops().sra_select(obj, u, pc)), [None] * 3
+    ob = _runs_of(obj, in_dims[0], B, 2, what)
+    check_small_caps(ob.shape[1], ob.shape[2], what)
+    out = _ext.ops().sra_small_select(ob, _runs_of(u, in_dims[1], B, 1, what), _front(pc, in_dims[2], B).reshape(B))
+    return list(out), [0] * 3
+
+
+def _sra_indicators(info, in_dims, obj):
+    if in_dims[0] is not None:
+        raise NotImplementedError("sra_indicators vmap rule: no batched form (SRA's batched runs go through sra_select, within its caps)")
+    return list(_ext.ops().sra_indicators(obj)), [None, None]
+
+
+def _sra_rank(info, in_dims, I1, I2, u, pc):
+    if any(d is not None for d in in_dims):
+        raise NotImplementedError("sra_rank vmap rule: no batched form (SRA's batched runs go through sra_select, within its caps)")
+    return _ext.ops().sra_rank(I1, I2, u, pc), None
+
+
 def register():
     """Install the rules (idempotent).  Without the compiled extension there is nothing to
     batch: CPU tensors never reach the HIP ops, and a device op raises on its own."""
@@ -330,6 +359,7 @@ def register():
                      ("moead_small_ask", _moead_small_ask), ("moead_small_tell", _moead_small_tell),
                      ("nsga3_associate", _nsga3_associate), ("nsga3_niche_select", _nsga3_niche_select),
                      ("hype_fitness", _hype_fitness), ("hv_count", _hv_count), ("hv_contrib", _hv_contrib),
-                     ("rvea_select", _rvea_select), ("rvea_cos_best", _rvea_cos_best)):
+                     ("rvea_select", _rvea_select), ("rvea_cos_best", _rvea_cos_best),
+                     ("sra_select", _sra_select), ("sra_indicators", _sra_indicators), ("sra_rank", _sra_rank)):
         torch.library.register_vmap(f"evoxmi::{name}", fn)
     _REGISTERED = True

@@ -1,5 +1,11 @@
 """SRA's environmental selection: the two indicators and their stochastic ranking
-(``sra_select.hip`` on a HIP device, the host op and the torch expressions on the CPU)."""
+(``sra_select.hip`` on a HIP device, the host op and the torch expressions on the CPU).
+
+``select`` does both.  On ``obj`` (B, n, m), and as ``sra_select`` under ``vmap`` (``evoxmi/ops/batching.py``), it selects for B
+independent runs in ONE launch of ``sra_small.hip``: a workgroup per run stages the run's rows in LDS, forms I1 and I2 in the
+summation order of the solo kernel (``csrc/include/evoxmi_sra.h`` holds the arithmetic for both files), and ranks them without
+writing them to global memory in between.  Every run gets the words of the 2-D call.  Its caps per run are ``N_SMALL_CAP`` rows at
+up to 8 objectives and half that at up to 16; above them it raises, it does not go run by run."""
 from __future__ import annotations
 
 import torch
@@ -9,6 +15,18 @@ from ..utils.common import cal_max
 
 RANK_CAP = 8192  # sra_select.hip, ranking: one workgroup, n ≤ 8192 rows
 INDICATOR_M_CAP = 16  # sra_select.hip, indicators: m ≤ 16 objectives
+N_SMALL_CAP = 2048  # sra_small.hip, a workgroup per run: n ≤ 2048 rows at m ≤ 8, n ≤ 1024 at m ≤ 16
+
+
+def small_ok(n: int, m: int) -> bool:
+    """Whether runs of n rows and m objectives fit the one-workgroup-per-run kernel."""
+    return n >= 1 and m >= 1 and ((m <= 8 and n <= N_SMALL_CAP) or (m <= INDICATOR_M_CAP and n <= N_SMALL_CAP // 2))
+
+
+def check_small_caps(n: int, m: int, what: str):
+    if not small_ok(n, m):
+        raise NotImplementedError(f"{what}: batched runs need 1 <= n <= {N_SMALL_CAP} rows at m <= 8 objectives or n <= {N_SMALL_CAP // 2} "
+                                  f"at m <= {INDICATOR_M_CAP} per run, got n = {n}, m = {m}")
 
 
 def on_device(n: int, m: int, device) -> bool:
@@ -78,3 +96,79 @@ def stochastic_rank(I1: torch.Tensor, I2: torch.Tensor, u: torch.Tensor, pc) -> 
         return _ext.ops().sra_rank(I1.to(torch.float32).contiguous(), I2.to(dev, torch.float32).contiguous(),
                                    u.to(dev, torch.float32).contiguous(), pc)
     return _stochastic_rank_host(I1, I2, u, pc)
+
+
+def _pc_word(pc, dev):
+    if isinstance(pc, torch.Tensor):
+        return pc.to(device=dev, dtype=torch.float32)
+    return torch.full((), float(pc), dtype=torch.float32, device=dev)  # a fill kernel, not an H2D copy
+
+
+def _select_runs(obj, u, pc, return_info):
+    B, n, m = obj.shape
+    if obj.is_cuda:
+        check_small_caps(n, m, "ops.sra.select")
+        out = _ext.ops().sra_small_select(obj.to(torch.float32).contiguous(), u.to(obj.device, torch.float32).contiguous(),
+                                          _pc_word(pc, obj.device).expand(B).contiguous())
+    else:
+        pcs = pc.expand(B) if isinstance(pc, torch.Tensor) else [pc] * B
+        out = [torch.stack(t) for t in zip(*(select(obj[r], u[r], pcs[r], True) for r in range(B)))]
+    return tuple(out) if return_info else out[0]
+
+
+def select(obj: torch.Tensor, u: torch.Tensor, pc, return_info: bool = False):
+    """The permutation (n,) int64, best first, of SRA's selection of the rows ``obj`` (n, m): ``indicators`` and then
+    ``stochastic_rank`` with the draws ``u`` (n − 1,) and ``pc``, a Python float or a 0-d tensor; ``return_info`` gives
+    ``(idx, I1, I2)``.  On a HIP device within the caps of ``on_device`` it is the two launches of ``sra_select.hip`` and reads
+    nothing on the host; elsewhere the dense torch expressions and ``stochastic_rank``, on the CPU the host op.
+
+    ``obj`` (B, n, m) selects for B independent runs: ``u`` is (B, n − 1), ``pc`` a float, a 0-d tensor or (B,), and every result
+    gains a leading run axis.  On a HIP device that is ONE launch of ``sra_small.hip``, a workgroup per run, whose words are those
+    of the 2-D call on each run; runs above its caps (``small_ok``) raise ``NotImplementedError``.  On the CPU the 2-D path runs
+    run by run."""
+    if obj.dim() == 3:
+        return _select_runs(obj, u, pc, return_info)
+    n, m = obj.shape
+    if on_device(n, m, obj.device):
+        dev = obj.device
+        idx, I1, I2 = _ext.ops().sra_select(obj.to(torch.float32).contiguous(), u.to(dev, torch.float32).contiguous(), _pc_word(pc, dev))
+    else:
+        I1, I2 = indicators_dense(obj)
+        idx = stochastic_rank(I1, I2, u, pc)
+    return (idx, I1, I2) if return_info else idx
+
+
+@torch.library.custom_op("evoxmi_py::sra_select_runs", mutates_args=())
+def _select_draw_runs(obj: torch.Tensor, u: torch.Tensor, draw: torch.Tensor) -> torch.Tensor:
+    """The CPU selection of SRA run by run on obj (B, n, m), u (B, n − 1) and the raw draws (B,) that give each run's pc, as the
+    solo path forms it: the host ranking loops on data and reads pc as a float, so ``vmap`` cannot trace through it; this op is
+    what a vmapped call reaches."""
+    return torch.stack([_select_draw(o, uu, d) for o, uu, d in zip(obj, u, draw)])
+
+
+@_select_draw_runs.register_fake
+def _(obj, u, draw):
+    return obj.new_empty(obj.shape[:2], dtype=torch.int64)
+
+
+def _select_draw(obj, u, draw):
+    I1, I2 = indicators_dense(obj)
+    return _stochastic_rank_host(I1, I2, u, float(draw) * 0.2 + 0.4)
+
+
+@torch.library.custom_op("evoxmi_py::sra_select_run", mutates_args=())
+def select_run(obj: torch.Tensor, u: torch.Tensor, draw: torch.Tensor) -> torch.Tensor:
+    """One run of ``sra_select_runs``; under ``vmap`` its rule calls that op."""
+    return _select_draw(obj, u, draw)
+
+
+@select_run.register_fake
+def _(obj, u, draw):
+    return obj.new_empty(obj.shape[:1], dtype=torch.int64)
+
+
+@torch.library.register_vmap("evoxmi_py::sra_select_run")
+def _(info, in_dims, obj, u, draw):
+    B = info.batch_size
+    front = [t.unsqueeze(0).expand((B,) + tuple(t.shape)) if d is None else t.movedim(d, 0) for t, d in zip((obj, u, draw), in_dims)]
+    return _select_draw_runs(*front), 0
