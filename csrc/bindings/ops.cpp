@@ -1908,6 +1908,31 @@ std::vector<at::Tensor> tdea_theta_rank(const at::Tensor& obj, const at::Tensor&
   return {t_rank, cls, val};
 }
 
+// tdea_theta_rank for B runs in one launch of tdea_small.hip: obj (B, n, m), w (nw, m) or (B, nw, m), theta (nw,) or (B, nw), mask
+// (B, n) → t_rank (B, n) float32, cls (B, n) int32, val (B, n) float64, every run the words of tdea_theta_rank on its slices
+std::vector<at::Tensor> tdea_small_theta_rank(const at::Tensor& obj, const at::Tensor& w, const at::Tensor& theta, const at::Tensor& mask) {
+  const char* op = "tdea_small_theta_rank";
+  CHECK_DEV(obj); CHECK_F32(obj); CHECK_CONTIG(obj); CHECK_DEV(w); CHECK_F32(w); CHECK_CONTIG(w);
+  CHECK_DEV(theta); CHECK_F32(theta); CHECK_CONTIG(theta); CHECK_DEV(mask); CHECK_CONTIG(mask);
+  TORCH_CHECK(obj.dim() == 3 && obj.size(0) >= 1, op, ": obj float32 (B, n, m)");
+  const int64_t B = obj.size(0), n = obj.size(1), m = obj.size(2);
+  TORCH_CHECK((w.dim() == 2 || (w.dim() == 3 && w.size(0) == B)) && w.size(-1) == m, op, ": w float32 (nw, m) or (B, nw, m)");
+  const int64_t nw = w.size(-2);
+  TORCH_CHECK((theta.dim() == 1 || (theta.dim() == 2 && theta.size(0) == B)) && theta.size(-1) == nw, op, ": theta float32 (nw,) or (B, nw)");
+  TORCH_CHECK(mask.scalar_type() == at::kBool && mask.dim() == 2 && mask.size(0) == B && mask.size(1) == n, op, ": mask bool (B, n)");
+  TORCH_CHECK(w.device() == obj.device() && theta.device() == obj.device() && mask.device() == obj.device(), op, ": one device");
+  TORCH_CHECK(evx_rvea_small_ok(n, nw, m), op, ": needs n <= 4096 rows and nw <= 2048 (m <= 4), 1024 (m <= 8) or 512 (m <= 16) directions per run, got n = ",
+              n, ", nw = ", nw, ", m = ", m);
+  c10::DeviceGuard g(obj.device());
+  auto t_rank = at::empty({B, n}, obj.options());
+  auto cls = at::empty({B, n}, obj.options().dtype(at::kInt));
+  auto val = at::empty({B, n}, obj.options().dtype(at::kDouble));
+  evx_tdea_small_theta_rank(obj.data_ptr<float>(), w.data_ptr<float>(), w.dim() == 3 ? nw * m : 0, theta.data_ptr<float>(),
+                            theta.dim() == 2 ? nw : 0, mask.data_ptr<bool>(), (int)B, (int)n, (int)nw, (int)m, cls.data_ptr<int>(),
+                            val.data_ptr<double>(), t_rank.data_ptr<float>(), cur_stream());
+  return {t_rank, cls, val};
+}
+
 at::Tensor sra_rank(const at::Tensor& I1, const at::Tensor& I2, const at::Tensor& u, const at::Tensor& pc) {
   CHECK_DEV(I1); CHECK_F32(I1); CHECK_CONTIG(I1); CHECK_DEV(I2); CHECK_F32(I2); CHECK_CONTIG(I2);
   CHECK_DEV(u); CHECK_F32(u); CHECK_CONTIG(u); CHECK_DEV(pc); CHECK_F32(pc);
@@ -2323,6 +2348,7 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("hv_exact(Tensor pT, Tensor vals, Tensor idx) -> Tensor");
   m.def("hv_contributions(Tensor pT, Tensor vals, Tensor idx) -> Tensor");
   m.def("tdea_theta_rank(Tensor obj, Tensor w, Tensor theta, Tensor mask) -> Tensor[]");
+  m.def("tdea_small_theta_rank(Tensor obj, Tensor w, Tensor theta, Tensor mask) -> Tensor[]");
   m.def("sra_rank(Tensor I1, Tensor I2, Tensor u, Tensor pc) -> Tensor");
   m.def("sra_indicators(Tensor obj) -> Tensor[]");
   m.def("sra_select(Tensor obj, Tensor u, Tensor pc) -> Tensor[]");
@@ -2436,6 +2462,7 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("hv_exact", &hv_exact);
   m.impl("hv_contributions", &hv_contributions);
   m.impl("tdea_theta_rank", &tdea_theta_rank);
+  m.impl("tdea_small_theta_rank", &tdea_small_theta_rank);
   m.impl("sra_rank", &sra_rank);
   m.impl("sra_indicators", &sra_indicators);
   m.impl("sra_select", &sra_select);

@@ -299,6 +299,12 @@ void evx_hv_contributions(const float* pT, const float* vals, const int64_t* idx
 // rank of every masked row among the masked rows of its cls, +inf outside the mask; theta is (nw,) float32
 void evx_tdea_theta_rank(const float* obj, const double* best, const int* arg, const float* theta, const bool* mask, int n, int m, int nw,
                          int* cls, double* val, float* t_rank, hipStream_t s);
+// tdea_small.hip: the same ranking for B runs in one launch, a workgroup per run with the run's normalised directions, cls and val
+// in LDS and no scratch.  obj (B, n, m), mask (B, n); w (nw, m) and theta (nw,) are read at run · w_run_stride and
+// run · theta_run_stride elements (0: shared by the runs) → cls, val, t_rank (B, n), run by run the words of evx_rvea_prepare,
+// evx_rvea_cos_best (mode 0) and the launcher above.  The shapes it takes are evx_rvea_small_ok(n, nw, m)'s
+void evx_tdea_small_theta_rank(const float* obj, const float* w, int64_t w_run_stride, const float* theta, int64_t theta_run_stride,
+                               const bool* mask, int B, int n, int nw, int m, int* cls, double* val, float* t_rank, hipStream_t s);
 // sra_select.hip: SRA's stochastic ranking (n ≤ evx_sra_rank_max_n(), pc one device word, rank (n,) best first)
 // and its two indicators in one pass (m ≤ evx_sra_indicators_max_m())
 int evx_sra_rank_max_n();

@@ -15,8 +15,11 @@
 #include <stdint.h>
 
 #include "evoxmi_launchers.h"
+#include "evoxmi_tdea.h"
 
 namespace {
+
+using namespace evx;  // the arithmetic both this file and tdea_small.hip use: evoxmi_tdea.h
 
 constexpr int TD_THREADS = 1024;
 constexpr int TD_WAVES = TD_THREADS / 64;
@@ -26,22 +29,11 @@ __global__ void tdea_val_kernel(const float* __restrict__ obj, const double* __r
                                 const float* __restrict__ theta, int n, int m, int nw, int* __restrict__ cls_out, double* __restrict__ val_out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  double s = 0.0;
-  for (int t = 0; t < m; ++t) {
-    const double d = (double)obj[(size_t)i * m + t];
-    s = t == 0 ? d * d : s + d * d;
-  }
-  const double nrm = sqrt(s);
-  int cls = arg[i];
-  cls = cls < 0 ? 0 : (cls >= nw ? nw - 1 : cls);  // a NaN row's −1
-  double c = best[i];
-  c = c < -1.0 ? -1.0 : (c > 1.0 ? 1.0 : c);
-  const double d1 = nrm * c;
-  double q = 1.0 - c * c;
-  if (q < 0.0) q = 0.0;
-  const double d2 = nrm * sqrt(q);
+  int cls;
+  double val;
+  td_cls_val(obj + (size_t)i * m, m, nw, best[i], arg[i], theta, cls, val);
   cls_out[i] = cls;
-  val_out[i] = d1 + (double)theta[cls] * d2;
+  val_out[i] = val;
 }
 
 __global__ void __launch_bounds__(TD_THREADS)
@@ -55,7 +47,6 @@ __global__ void __launch_bounds__(TD_THREADS)
   const bool scan = live && mask[i];
   const int ci = scan ? cls[i] : -2;
   const double vi = scan ? val[i] : 0.0;
-  const bool nan_i = vi != vi;
   int count = 0;
   for (int j0 = 0; j0 < n; j0 += TD_TILE) {
     const int w = min(TD_TILE, n - j0);
@@ -70,13 +61,7 @@ __global__ void __launch_bounds__(TD_THREADS)
         if (tcls[jj] != ci) continue;
         const double vj = tval[jj];
         const int j = j0 + jj;
-        const bool nan_j = vj != vj;
-        bool before;
-        if (nan_i || nan_j)
-          before = nan_i && (!nan_j || j < i);
-        else
-          before = vj < vi || (vj == vi && j < i);
-        count += before ? 1 : 0;
+        count += td_before(vj, j, vi, i) ? 1 : 0;
       }
     }
   }

@@ -58,7 +58,15 @@ for one run, is ONE launch of ``rvea_small.hip`` for all of them, a workgroup pe
 vectors, γ and the per-vector minima in LDS (no scratch, no global atomics), each run with its own adapted vectors and θ.  It gives
 every run the words of the solo kernels, for merged populations of at most 4096 rows and 2048, 1024 or 512 reference vectors at up to
 4, 8 or 16 objectives per run (``NotImplementedError`` above); the rest of its tell is torch ops that ``vmap`` batches itself.
-RVEA*, LMOCSO and θ-DEA, which share the solo kernels, are not covered: their ``rvea_cos_best`` raises under ``vmap``.
+RVEA* and LMOCSO, which share the solo kernels, are not covered: their ``rvea_cos_best`` raises under ``vmap``.
+
+θ-DEA batches (``tests/test_batched_tdea.py``, ``tests/test_batched_tdea_gpu.py``): on a HIP device its θ-ranking, four launches for one
+run, is ONE launch of ``tdea_small.hip`` for all of them, a workgroup per run that keeps the run's normalised directions, θ, and then
+cls, val and the clusters' member lists in LDS (no scratch, no global atomics) and counts a row's rank inside its own cluster only.  It
+gives every run the words of the solo kernels, within the caps of RVEA's batched selection (``NotImplementedError`` above) and the
+non-dominated sort's 8192 rows and 8 objectives; the rest of its tell is torch ops that ``vmap`` batches itself.  On the CPU its
+non-dominated sort and its θ-ranking run run by run inside Python-registered ops (``evoxmi.ops.nds.rank_under_vmap``,
+``evoxmi_py::tdea_theta_rank_run``).
 
 SRA batches (``tests/test_batched_sra.py``, ``tests/test_batched_sra_gpu.py``): on a HIP device its selection, two launches for one
 run with the ranking on a single compute unit, is ONE launch of ``sra_small.hip`` for all runs, a workgroup per run that forms both
@@ -66,7 +74,10 @@ indicators from the run's rows in LDS and ranks them without writing them to glo
 gives every run the words of the solo kernels, for merged populations of at most 2048 rows at up to 8 objectives and 1024 at up to 16
 (``NotImplementedError`` above).  On the CPU the selection runs run by run inside a Python-registered op (``evoxmi.ops.sra.select_run``).
 
-Covered multi-objective algorithms: NSGA-II, GDE3, IBEA, SPEA2, MOEA/D, NSGA-III, HypE, RVEA, SRA.  The others are not, and an uncovered
+On the CPU the float32 powers of SBX and polynomial mutation are taken run by run under ``vmap`` (``utils.common.pow_under_vmap``):
+torch's CPU ``pow`` rounds an element by its place in the tensor, so the power of the stacked runs is not the power of each run.
+
+Covered multi-objective algorithms: NSGA-II, GDE3, IBEA, SPEA2, MOEA/D, NSGA-III, HypE, RVEA, SRA, θ-DEA.  The others are not, and an uncovered
 one is not guaranteed to raise, though most do, from ``vmap`` (their selections read the host or loop on data) or from an op's rule:
 do not rely on ``BatchedRuns`` over an algorithm that is not listed here.
 """

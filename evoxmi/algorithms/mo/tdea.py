@@ -14,7 +14,8 @@ import torch
 
 from ...core import State
 from ...operators.sampling import UniformSampling
-from ...operators.selection.non_dominate import lexsort, non_dominated_sort
+from ...operators.selection.non_dominate import lexsort
+from ...ops import nds as nds_ops
 from ...ops import random as rnd
 from ...ops import tdea as tdea_ops
 from ...utils.common import cos_dist
@@ -73,7 +74,7 @@ class TDEA(MOAlgorithm):
         N, m = self.pop_size, self.n_objs
         pop = torch.cat([state.population, state.next_generation], 0)
         obj = torch.cat([state.fitness, fitness], 0)
-        rank = non_dominated_sort(obj, until=N + 1)
+        rank = nds_ops.rank_under_vmap(obj, until=N + 1)  # non_dominated_sort, run by run where BatchedRuns vmaps the CPU path
         worst = torch.sort(rank).values[N]
         mask = rank <= worst
         z = torch.minimum(state.z, obj.min(0).values)

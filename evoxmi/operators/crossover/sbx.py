@@ -5,6 +5,7 @@ from __future__ import annotations
 import torch
 
 from ...ops import random as rnd
+from ...utils.common import pow_under_vmap as _pow  # x ** e, run by run where BatchedRuns vmaps the CPU path
 
 
 def simulated_binary(key, x, pro_c=1.0, dis_c=20.0, type=1, cols=None):
@@ -32,7 +33,7 @@ def simulated_binary(key, x, pro_c=1.0, dis_c=20.0, type=1, cols=None):
     dev = x.device
     w = rnd.bits(gene_key, (n_p, dt)).to(dev)[:, c0 : c0 + d]
     mu = rnd._u24(w)
-    beta = torch.where(mu <= 0.5, (2 * mu) ** (1 / (dis_c + 1)), (2 - 2 * mu) ** (-1 / (dis_c + 1)))
+    beta = torch.where(mu <= 0.5, _pow(2 * mu, 1 / (dis_c + 1)), _pow(2 - 2 * mu, -1 / (dis_c + 1)))
     beta = torch.where((w & 1) == 1, -beta, beta)
     beta = torch.where(((w >> 1) & 1) == 1, torch.ones_like(beta), beta)
     beta = torch.where((rnd.uniform(pair_key, (n_p, 1)).to(dev) > pro_c).expand(n_p, d), torch.ones_like(beta), beta)

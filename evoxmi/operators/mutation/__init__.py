@@ -4,6 +4,7 @@ from __future__ import annotations
 import torch
 
 from ...ops import random as rnd
+from ...utils.common import pow_under_vmap as _pow  # x ** e, run by run where BatchedRuns vmaps the CPU path
 
 
 def polynomial(key, x, boundary, pro_m=1.0, dis_m=20.0, cols=None):
@@ -28,10 +29,10 @@ def polynomial(key, x, boundary, pro_m=1.0, dis_m=20.0, cols=None):
     pop = torch.maximum(torch.minimum(pop, upper), lower)
     temp = site & (mu <= 0.5)
     norm = torch.where(temp, (pop - lower) / (upper - lower), torch.zeros_like(pop))
-    pop = torch.where(temp, pop + (upper - lower) * ((2.0 * mu + (1.0 - 2.0 * mu) * (1.0 - norm) ** (dis_m + 1.0)) ** (1.0 / (dis_m + 1)) - 1.0), pop)
+    pop = torch.where(temp, pop + (upper - lower) * (_pow(2.0 * mu + (1.0 - 2.0 * mu) * _pow(1.0 - norm, dis_m + 1.0), 1.0 / (dis_m + 1)) - 1.0), pop)
     temp = site & (mu > 0.5)
     norm = torch.where(temp, (upper - pop) / (upper - lower), torch.zeros_like(pop))
-    pop = torch.where(temp, pop + (upper - lower) * (1.0 - (2.0 * (1.0 - mu) + 2.0 * (mu - 0.5) * (1.0 - norm) ** (dis_m + 1.0)) ** (1.0 / (dis_m + 1.0))), pop)
+    pop = torch.where(temp, pop + (upper - lower) * (1.0 - _pow(2.0 * (1.0 - mu) + 2.0 * (mu - 0.5) * _pow(1.0 - norm, dis_m + 1.0), 1.0 / (dis_m + 1.0))), pop)
     if x.shape[0] % 2 != 0 and x.shape[0] != 1:
         pop = torch.cat([pop, x[-1:]], 0)
     return pop

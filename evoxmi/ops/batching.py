@@ -34,6 +34,10 @@ per run).  Each rule moves the run axis to the front and calls the op's batched 
   normalised vectors in LDS (``rvea_small.hip``; n ≤ 4096 and nv ≤ 2048, 1024 or 512 for m ≤ 4, 8 or 16 per run); an unbatched
   operand is broadcast.  Every output of run r is the 2-D op's on that run, bit for bit (``tests/test_batched_rvea_gpu.py``).
   ``rvea_cos_best`` has no batched form: its rule passes unbatched calls through and raises on batched operands.;
+* ``tdea_theta_rank``: obj (B, n, m), mask (B, n), w (nw, m) or (B, nw, m), θ (nw,) or (B, nw) → ``tdea_small_theta_rank``, one
+  workgroup per run that keeps the run's normalised directions, then cls and val and the clusters' member lists in LDS
+  (``tdea_small.hip``; the caps of ``rvea_small_select``).  Directions that are not batched stay shared.  Every output of run r is
+  the 2-D op's on that run, bit for bit (``tests/test_batched_tdea_gpu.py``);
 * ``sra_select``: obj (B, n, m), u (B, n − 1), pc (B,) → ``sra_small_select``, one workgroup per run that forms both indicators and
   ranks the rows without writing the indicators to global memory in between (``sra_small.hip``; n ≤ 2048 at m ≤ 8, n ≤ 1024 at
   m ≤ 16 per run); an unbatched operand is broadcast.  Every output of run r is the 2-D op's on that run, bit for bit
@@ -317,9 +321,22 @@ def _rvea_select(info, in_dims, f, shift, floor, v, theta):
 
 def _rvea_cos_best(info, in_dims, A, shift, floor, B, clamp, self_zero):
     if any(d is not None for d in in_dims):
-        raise NotImplementedError("rvea_cos_best vmap rule: no batched form (RVEA's batched runs go through rvea_select, within its caps; "
-                                  "RVEA*, LMOCSO and θ-DEA are not covered)")
+        raise NotImplementedError("rvea_cos_best vmap rule: no batched form (RVEA's batched runs go through rvea_select and θ-DEA's "
+                                  "through tdea_theta_rank, within their caps; RVEA* and LMOCSO are not covered)")
     return list(_ext.ops().rvea_cos_best(A, shift, floor, B, clamp, self_zero)), [None, None]
+
+
+def _tdea_theta_rank(info, in_dims, obj, w, theta, mask):
+    from .rvea import check_small_caps
+
+    B, what = info.batch_size, "tdea_theta_rank vmap rule"
+    if all(d is None for d in in_dims):
+        return list(_ext.ops().tdea_theta_rank(obj, w, theta, mask)), [None] * 3
+    ob = _runs_of(obj, in_dims[0], B, 2, what)
+    wb = w if in_dims[1] is None else _runs_of(w, in_dims[1], B, 2, what)  # directions the runs share stay (nw, m)
+    tb = theta if in_dims[2] is None else _runs_of(theta, in_dims[2], B, 1, what)
+    check_small_caps(ob.shape[1], wb.shape[-2], ob.shape[2], what)
+    return list(_ext.ops().tdea_small_theta_rank(ob, wb, tb, _runs_of(mask, in_dims[3], B, 1, what))), [0, 0, 0]
 
 
 def _sra_select(info, in_dims, obj, u, pc):
@@ -359,7 +376,7 @@ def register():
                      ("moead_small_ask", _moead_small_ask), ("moead_small_tell", _moead_small_tell),
                      ("nsga3_associate", _nsga3_associate), ("nsga3_niche_select", _nsga3_niche_select),
                      ("hype_fitness", _hype_fitness), ("hv_count", _hv_count), ("hv_contrib", _hv_contrib),
-                     ("rvea_select", _rvea_select), ("rvea_cos_best", _rvea_cos_best),
+                     ("rvea_select", _rvea_select), ("rvea_cos_best", _rvea_cos_best), ("tdea_theta_rank", _tdea_theta_rank),
                      ("sra_select", _sra_select), ("sra_indicators", _sra_indicators), ("sra_rank", _sra_rank)):
         torch.library.register_vmap(f"evoxmi::{name}", fn)
     _REGISTERED = True

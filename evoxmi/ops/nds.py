@@ -149,30 +149,31 @@ def nsga2_survivors_torch(f: torch.Tensor, N: int, mask_pos: int, until: int = 0
 
 
 @torch.library.custom_op("evoxmi_py::nds_rank_run", mutates_args=())
-def _rank_run(f: torch.Tensor) -> torch.Tensor:
+def _rank_run(f: torch.Tensor, until: int = 0) -> torch.Tensor:
     from ..operators.selection.non_dominate import non_dominated_sort as nds_any
 
-    return nds_any(f)  # (n, m), or (B, n, m) run by run
+    return nds_any(f, until=until)  # (n, m), or (B, n, m) run by run
 
 
 @_rank_run.register_fake
-def _(f):
+def _(f, until=0):
     return f.new_empty(f.shape[:-1], dtype=torch.int32)
 
 
 @torch.library.register_vmap("evoxmi_py::nds_rank_run")
-def _(info, in_dims, f):
-    return _rank_run(f.movedim(in_dims[0], 0)), 0
+def _(info, in_dims, f, until=0):
+    return _rank_run(f.movedim(in_dims[0], 0), until), 0
 
 
-def rank_under_vmap(f: torch.Tensor) -> torch.Tensor:
-    """Pareto ranks of f (n, m) where the caller may be a run of ``BatchedRuns``: the CPU peel loop is data-dependent, so under
-    ``vmap`` it runs run by run inside a Python-registered op; a device tensor takes ``non_dominated_sort`` and its batched rule."""
+def rank_under_vmap(f: torch.Tensor, until: int = 0) -> torch.Tensor:
+    """Pareto ranks of f (n, m), peeled as far as ``until`` asks (``non_dominated_sort``), where the caller may be a run of
+    ``BatchedRuns``: the CPU peel loop is data-dependent, so under ``vmap`` it runs run by run inside a Python-registered op; a
+    device tensor takes ``non_dominated_sort`` and its batched rule."""
     if not f.is_cuda and _in_vmap(f):
-        return _rank_run(f)
+        return _rank_run(f, int(until))
     from ..operators.selection.non_dominate import non_dominated_sort as nds_any
 
-    return nds_any(f)
+    return nds_any(f, until=until)
 
 
 NICHE_SELECT_CAP = 8192  # nsga3_select.hip: one workgroup, n ≤ 8192 rows and R ≤ 8192 niches

@@ -70,6 +70,30 @@ def cal_max(x, y):
     return (x[:, None, :] - y[None, :, :]).amax(-1)
 
 
+@torch.library.custom_op("evoxmi_py::pow_run", mutates_args=())
+def _pow_run(x: torch.Tensor, exponent: float) -> torch.Tensor:
+    return x**exponent
+
+
+@_pow_run.register_fake
+def _(x, exponent):
+    return torch.empty_like(x)
+
+
+@torch.library.register_vmap("evoxmi_py::pow_run")
+def _(info, in_dims, x, exponent):
+    return torch.stack([xr.contiguous() ** exponent for xr in x.movedim(in_dims[0], 0)]), 0
+
+
+def pow_under_vmap(x, exponent: float):
+    """``x ** exponent`` where the caller may be a run of ``BatchedRuns``.  The CPU's float32 ``pow`` rounds an element by where it
+    lies in its tensor (the vector loop and its scalar tail differ in the last bit), so under ``vmap`` the power of the stacked runs
+    is not the power of each run: there it is taken run by run inside a Python-registered op.  Elsewhere it is ``x ** exponent``."""
+    if not x.is_cuda and torch._C._functorch.is_batchedtensor(x):
+        return _pow_run(x, float(exponent))
+    return x**exponent
+
+
 def dominate(x, y):
     return bool(torch.all(x <= y) & torch.any(x < y))
 
