@@ -1848,6 +1848,30 @@ std::vector<at::Tensor> bige_estimate(const at::Tensor& fit, const at::Tensor& m
   return {bi, pr, cd};
 }
 
+// bige_estimate and the non-dominated sort of its bi for B runs in one launch of bige_small.hip: fit (B, n, m), mask (B, n), r (B,), one
+// float32 word per run → bi (B, n, 2) float32, rank (B, n) int32, pr and cd (B, n) float64, every run the words of bige_estimate and
+// nds on its slices
+std::vector<at::Tensor> bige_small_estimate_rank(const at::Tensor& fit, const at::Tensor& mask, const at::Tensor& r) {
+  const char* op = "bige_small_estimate_rank";
+  CHECK_DEV(fit); CHECK_F32(fit); CHECK_CONTIG(fit); CHECK_DEV(mask); CHECK_CONTIG(mask); CHECK_DEV(r); CHECK_F32(r); CHECK_CONTIG(r);
+  TORCH_CHECK(fit.dim() == 3 && fit.size(0) >= 1, op, ": fit float32 (B, n, m)");
+  const int64_t B = fit.size(0), n = fit.size(1), m = fit.size(2);
+  TORCH_CHECK(mask.scalar_type() == at::kBool && mask.dim() == 2 && mask.size(0) == B && mask.size(1) == n, op, ": mask bool (B, n)");
+  TORCH_CHECK(r.dim() == 1 && r.size(0) == B, op, ": r float32 (B,), one device word per run");
+  TORCH_CHECK(mask.device() == fit.device() && r.device() == fit.device(), op, ": one device");
+  TORCH_CHECK(evx_bige_small_ok(n, m), op, ": needs 1 <= n <= 2048 (m <= 4), 1024 (m <= 8) or 512 (m <= 16) rows per run, got n = ", n,
+              ", m = ", m);
+  c10::DeviceGuard g(fit.device());
+  auto f64 = fit.options().dtype(at::kDouble);
+  auto bi = at::empty({B, n, 2}, fit.options());
+  auto rank = at::empty({B, n}, fit.options().dtype(at::kInt));
+  auto pr = at::empty({B, n}, f64);
+  auto cd = at::empty({B, n}, f64);
+  evx_bige_small_estimate_rank(fit.data_ptr<float>(), mask.data_ptr<bool>(), r.data_ptr<float>(), (int)B, (int)n, (int)m, bi.data_ptr<float>(),
+                               rank.data_ptr<int32_t>(), pr.data_ptr<double>(), cd.data_ptr<double>(), cur_stream());
+  return {bi, rank, pr, cd};
+}
+
 // hv_exact.hip: the total (a 0-d float64) or the contributions (n,) float64 of the boxes [0, p_i].  pT is the (m, n) transpose of the
 // points clamped at 0, vals and idx its rows sorted descending by a stable sort (evoxmi/ops/hv.py does that)
 static at::Tensor hv_run(const char* name, const at::Tensor& pT, const at::Tensor& vals, const at::Tensor& idx, bool contributions) {
@@ -2345,6 +2369,7 @@ TORCH_LIBRARY(evoxmi, m) {
   m.def("rvea_select(Tensor f, Tensor? shift, float? floor, Tensor v, Tensor theta) -> Tensor[]");
   m.def("rvea_small_select(Tensor f, Tensor shift, float floor, Tensor v, Tensor theta) -> Tensor[]");
   m.def("bige_estimate(Tensor fit, Tensor mask, Tensor r) -> Tensor[]");
+  m.def("bige_small_estimate_rank(Tensor fit, Tensor mask, Tensor r) -> Tensor[]");
   m.def("hv_exact(Tensor pT, Tensor vals, Tensor idx) -> Tensor");
   m.def("hv_contributions(Tensor pT, Tensor vals, Tensor idx) -> Tensor");
   m.def("tdea_theta_rank(Tensor obj, Tensor w, Tensor theta, Tensor mask) -> Tensor[]");
@@ -2459,6 +2484,7 @@ TORCH_LIBRARY_IMPL(evoxmi, CUDA, m) {
   m.impl("rvea_select", &rvea_select);
   m.impl("rvea_small_select", &rvea_small_select);
   m.impl("bige_estimate", &bige_estimate);
+  m.impl("bige_small_estimate_rank", &bige_small_estimate_rank);
   m.impl("hv_exact", &hv_exact);
   m.impl("hv_contributions", &hv_contributions);
   m.impl("tdea_theta_rank", &tdea_theta_rank);

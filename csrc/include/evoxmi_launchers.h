@@ -284,6 +284,13 @@ void evx_rvea_small_select(const float* f, const float* shift, double floor_v, c
 // word
 void evx_bige_estimate(const float* f, const bool* mask, const float* r, int n, int m, float* fmin, float* fmax, double* x, double* prs,
                        float* bi, double* pr, double* cd, hipStream_t s);
+// bige_small.hip: the same estimate and the Pareto rank of its bi-goal points for B runs in one launch, a workgroup per run with the
+// run's normalised rows, pr and the bi-goal pairs in LDS and no scratch.  f (B, n, m), mask (B, n), r (B,) → bi (B, n, 2), rank, pr, cd
+// (B, n), run by run the words of the launcher above and of evx_nds on its bi.  evx_bige_small_ok: the shapes it takes (m ≤ 16,
+// n · MC ≤ 8192 for MC = 4, 8, 16 the padded m)
+bool evx_bige_small_ok(int64_t n, int64_t m);
+void evx_bige_small_estimate_rank(const float* f, const bool* mask, const float* r, int B, int n, int m, float* bi, int32_t* rank, double* pr,
+                                  double* cd, hipStream_t s);
 // hv_exact.hip: the exact hypervolume of the boxes [0, p_i] (m = 2, 3, 4) and every row's exclusive contribution (m = 2, 3); the
 // contract is in evoxmi/ops/hv.py.  pT is the (m, n) transpose of the points clamped at 0, vals and idx (m, n) its rows sorted
 // descending by a stable sort and their original positions.  Scratch of n words each: zrank, wrank, orig, X, Y, ZW, h, g (and

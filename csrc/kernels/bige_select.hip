@@ -24,9 +24,12 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "evoxmi_bige.h"
 #include "evoxmi_launchers.h"
 
 namespace {
+
+using namespace evx;  // the arithmetic both this file and bige_small.hip use: evoxmi_bige.h
 
 constexpr int BG_THREADS = 1024;
 constexpr int BG_WAVES = BG_THREADS / 64;
@@ -64,21 +67,7 @@ __global__ void bige_prepare_kernel(const float* __restrict__ f, const bool* __r
                                     const float* __restrict__ fmax, double* __restrict__ x, double* __restrict__ pr) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  if (!mask[i]) {
-    for (int t = 0; t < m; ++t) x[(size_t)t * n + i] = INFINITY;
-    pr[i] = INFINITY;
-    return;
-  }
-  double s = 0.0;
-  for (int t = 0; t < m; ++t) {
-    const double lo = (double)fmin[t];
-    double span = (double)fmax[t] - lo;
-    if (!(span >= 1e-6)) span = 1e-6;
-    const double v = ((double)f[(size_t)i * m + t] - lo) / span;
-    x[(size_t)t * n + i] = v;
-    s = t == 0 ? v : s + v;
-  }
-  pr[i] = s;
+  pr[i] = bg_normalise_row(f + (size_t)i * m, mask[i], m, fmin, fmax, x + i, (size_t)n);
 }
 
 template <int MC>
@@ -93,7 +82,7 @@ __global__ void __launch_bounds__(BG_THREADS)
   const bool live = i < n;
   const bool scan = live && mask[i];
   const double r = (double)r_in[0];
-  const double rr_hi = (r * r) * (1.0 + 0x1p-40);
+  const double rr_hi = bg_prefilter(r);
   double a[MC];
 #pragma unroll
   for (int t = 0; t < MC; ++t) a[t] = 0.0;
@@ -116,37 +105,13 @@ __global__ void __launch_bounds__(BG_THREADS)
     for (int jj = threadIdx.x; jj < w; jj += BG_THREADS) tpr[jj] = pr[j0 + jj];
     __syncthreads();
     if (scan) {
-      for (int jj = lane; jj < w; jj += 64) {
-        double d2 = 0.0;
-#pragma unroll
-        for (int t = 0; t < MC; ++t)
-          if (t < m) {
-            const double dl = a[t] - tile[t * TJ + jj];
-            const double p = dl * dl;
-            d2 = t == 0 ? p : d2 + p;
-          }
-        if (d2 < rr_hi && j0 + jj != i) {  // a NaN fails the test
-          const double d = sqrt(d2);
-          if (d2 == 0.0 && 0.0 < r) {
-            dup += 1;  // an equal row: equal x, so equal pr, w = 2 and sh = (0.5 · (2 · (1 − 0 / r)))² = 1 exactly
-          } else if (d < r) {
-            const double pj = tpr[jj];
-            const double wgt = 1.0 + (pi >= pj ? 1.0 : 0.0) + (pi > pj ? 1.0 : 0.0);
-            const double h = 0.5 * (wgt * (1.0 - d / r));
-            acc += h * h;
-          }
-        }
-      }
+      for (int jj = lane; jj < w; jj += 64) bg_pair<MC>(a, tile + jj, TJ, m, j0 + jj == i, pi, tpr + jj, r, rr_hi, acc, dup);
     }
   }
   if (!live) return;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    acc += __shfl_xor(acc, off);
-    dup += __shfl_xor(dup, off);
-  }
+  const double sum = bg_wave_cd(acc, dup);
   if (lane != 0) return;
-  const double cd = scan ? sqrt(acc + (double)dup) : INFINITY;
+  const double cd = scan ? sum : INFINITY;
   const double p = scan ? pi : INFINITY;
   pr_out[i] = p;
   cd_out[i] = cd;

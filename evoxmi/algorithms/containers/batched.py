@@ -74,10 +74,18 @@ indicators from the run's rows in LDS and ranks them without writing them to glo
 gives every run the words of the solo kernels, for merged populations of at most 2048 rows at up to 8 objectives and 1024 at up to 16
 (``NotImplementedError`` above).  On the CPU the selection runs run by run inside a Python-registered op (``evoxmi.ops.sra.select_run``).
 
+BiGE batches (``tests/test_batched_bige.py``, ``tests/test_batched_bige_gpu.py``): on a HIP device a bi-goal estimate and the
+non-dominated sort of its result, three launches and a sort for one run, are ONE launch of ``bige_small.hip`` for all runs, a workgroup
+per run that keeps the run's normalised rows and proximities in LDS (no scratch, no global atomics), forms the crowding degree in the
+solo kernel's sum order and ranks the bi-goal pairs there.  It gives every run the words of the solo kernels, for merged populations of
+at most 2048, 1024 or 512 rows at up to 4, 8 or 16 objectives per run (``NotImplementedError`` above) and the non-dominated sort's 8
+objectives.  On the CPU its non-dominated sort and its estimate run run by run inside Python-registered ops
+(``evoxmi.ops.nds.rank_under_vmap``, ``evoxmi_py::bige_estimate_rank_run``).
+
 On the CPU the float32 powers of SBX and polynomial mutation are taken run by run under ``vmap`` (``utils.common.pow_under_vmap``):
 torch's CPU ``pow`` rounds an element by its place in the tensor, so the power of the stacked runs is not the power of each run.
 
-Covered multi-objective algorithms: NSGA-II, GDE3, IBEA, SPEA2, MOEA/D, NSGA-III, HypE, RVEA, SRA, θ-DEA.  The others are not, and an uncovered
+Covered multi-objective algorithms: NSGA-II, GDE3, IBEA, SPEA2, MOEA/D, NSGA-III, HypE, RVEA, SRA, θ-DEA, BiGE.  The others are not, and an uncovered
 one is not guaranteed to raise, though most do, from ``vmap`` (their selections read the host or loop on data) or from an op's rule:
 do not rely on ``BatchedRuns`` over an algorithm that is not listed here.
 """

@@ -6,16 +6,18 @@ non-dominated sorting in that bi-goal space.  The reference's ``ask`` estimates 
 bi-goal values from the *decision vectors* (``bige.py:110``); the objectives are used
 here, as in the method.
 
-``ask`` and ``tell`` estimate with ``ops.bige.estimate``: ``bige_select.hip`` on a HIP device (float64, no (n, n)
-array), and ``estimate`` below, the dense float32 expression, on the CPU and above the kernels' caps.
+``ask`` and ``tell`` estimate and rank with ``ops.bige.estimate_rank``: ``bige_select.hip`` on a HIP device (float64, no (n, n)
+array), and ``estimate`` below, the dense float32 expression, on the CPU and above the kernels' caps, each followed by the
+non-dominated sort of the bi-goal points.  Under ``BatchedRuns`` an estimate and its sort are one launch of ``bige_small.hip`` for
+all runs, a workgroup per run.
 """
 from __future__ import annotations
 
 import torch
 
 from ...operators import selection
-from ...operators.selection.non_dominate import non_dominated_sort
 from ...ops import bige as bige_ops
+from ...ops import nds as nds_ops
 from ...ops import random as rnd
 from .common import MOAlgorithm
 
@@ -46,19 +48,19 @@ class BiGE(MOAlgorithm):
 
     def ask(self, state):
         k0, k1, k2, k3 = rnd.split(state.key, 4)
-        bi = bige_ops.estimate(state.fitness, torch.ones(self.pop_size, dtype=torch.bool, device=state.fitness.device))
-        selected, _ = self.selection(k1, state.population, non_dominated_sort(bi).to(torch.float32))
+        _, bi_rank = bige_ops.estimate_rank(state.fitness, torch.ones(self.pop_size, dtype=torch.bool, device=state.fitness.device))
+        selected, _ = self.selection(k1, state.population, bi_rank.to(torch.float32))
         off = self._variation(k2, k3, selected)
         return off, state.update(next_generation=off, key=k0)
 
     def tell(self, state, fitness):
         merged_pop = torch.cat([state.population, state.next_generation], 0)
         merged_fit = torch.cat([state.fitness, fitness], 0)
-        rank = non_dominated_sort(merged_fit)
+        rank = nds_ops.rank_under_vmap(merged_fit)  # non_dominated_sort, run by run where BatchedRuns vmaps the CPU path
         order = torch.argsort(rank, stable=True)
         rank, pop, fit = rank[order], merged_pop[order], merged_fit[order]
         last = rank[self.pop_size]
-        bi_rank = non_dominated_sort(bige_ops.estimate(fit, rank == last))
+        _, bi_rank = bige_ops.estimate_rank(fit, rank == last)
         fin = torch.where(rank >= last, bi_rank, torch.full_like(bi_rank, -1))
         idx = torch.argsort(fin, stable=True)[: self.pop_size]
         return state.update(population=pop[idx], fitness=fit[idx])

@@ -38,6 +38,12 @@ per run).  Each rule moves the run axis to the front and calls the op's batched 
   workgroup per run that keeps the run's normalised directions, then cls and val and the clusters' member lists in LDS
   (``tdea_small.hip``; the caps of ``rvea_small_select``).  Directions that are not batched stay shared.  Every output of run r is
   the 2-D op's on that run, bit for bit (``tests/test_batched_tdea_gpu.py``);
+* ``bige_small_estimate_rank``: fit (B, n, m), mask (B, n), r (B,) → itself, one workgroup per run that keeps the run's normalised
+  rows in LDS, forms the bi-goal estimate and ranks its points there (``bige_small.hip``; n ≤ 2048, 1024 or 512 for m ≤ 4, 8 or 16
+  per run); ``ops.bige.estimate_rank`` calls it with a run's own operands under ``vmap``, and an unbatched operand is broadcast.
+  Every output of run r is ``bige_estimate``'s and the non-dominated sort's on that run, bit for bit
+  (``tests/test_batched_bige_gpu.py``).  ``bige_estimate`` has no batched form: its rule passes unbatched calls through and raises
+  on batched operands;
 * ``sra_select``: obj (B, n, m), u (B, n − 1), pc (B,) → ``sra_small_select``, one workgroup per run that forms both indicators and
   ranks the rows without writing the indicators to global memory in between (``sra_small.hip``; n ≤ 2048 at m ≤ 8, n ≤ 1024 at
   m ≤ 16 per run); an unbatched operand is broadcast.  Every output of run r is the 2-D op's on that run, bit for bit
@@ -339,6 +345,23 @@ def _tdea_theta_rank(info, in_dims, obj, w, theta, mask):
     return list(_ext.ops().tdea_small_theta_rank(ob, wb, tb, _runs_of(mask, in_dims[3], B, 1, what))), [0, 0, 0]
 
 
+def _bige_small_estimate_rank(info, in_dims, fit, mask, r):
+    from .bige import check_small_caps
+
+    B, what = info.batch_size, "bige_small_estimate_rank vmap rule"
+    fb = _runs_of(fit, in_dims[0], B, 2, what)
+    check_small_caps(fb.shape[1], fb.shape[2], what)
+    out = _ext.ops().bige_small_estimate_rank(fb, _runs_of(mask, in_dims[1], B, 1, what), _front(r, in_dims[2], B).reshape(B))
+    return list(out), [0] * 4
+
+
+def _bige_estimate(info, in_dims, fit, mask, r):
+    if any(d is not None for d in in_dims):
+        raise NotImplementedError("bige_estimate vmap rule: no batched form (BiGE's batched runs go through bige_small_estimate_rank, "
+                                  "within its caps)")
+    return list(_ext.ops().bige_estimate(fit, mask, r)), [None] * 3
+
+
 def _sra_select(info, in_dims, obj, u, pc):
     from .sra import check_small_caps
 
@@ -377,6 +400,7 @@ def register():
                      ("nsga3_associate", _nsga3_associate), ("nsga3_niche_select", _nsga3_niche_select),
                      ("hype_fitness", _hype_fitness), ("hv_count", _hv_count), ("hv_contrib", _hv_contrib),
                      ("rvea_select", _rvea_select), ("rvea_cos_best", _rvea_cos_best), ("tdea_theta_rank", _tdea_theta_rank),
+                     ("bige_small_estimate_rank", _bige_small_estimate_rank), ("bige_estimate", _bige_estimate),
                      ("sra_select", _sra_select), ("sra_indicators", _sra_indicators), ("sra_rank", _sra_rank)):
         torch.library.register_vmap(f"evoxmi::{name}", fn)
     _REGISTERED = True

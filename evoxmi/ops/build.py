@@ -89,6 +89,8 @@ def _run(cmd):
 # penalised distance bit for bit
 # tdea_small.hip: the batched form of rvea_select.hip's cosines and tdea_select.hip; its runs must equal those files' launches bit for
 # bit (shared arithmetic: evoxmi_rvea.h, evoxmi_tdea.h)
+# bige_small.hip: the batched form of bige_select.hip; its runs must equal that file's launches bit for bit (shared arithmetic:
+# evoxmi_bige.h)
 # nsga3_assoc.hip: the same kind of contract (NSGA-III's nadir and perpendicular distances), and the solo and the batched call
 # share its kernels bit for bit; it is float64 throughout, so packed f32 arithmetic is switched off for it
 # hype_fitness.hip: its samples are u · (ref − fmin) + fmin with two roundings, bit for bit the torch expression they replace
@@ -103,7 +105,8 @@ def _run(cmd):
 FILE_FLAGS = {"cma_small.hip": ["-ffp-contract=fast-honor-pragmas", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "eigh_sbr.hip": ["-fno-slp-vectorize"], "mo_geom.hip": ["-ffp-contract=fast-honor-pragmas"],
               "knea_select.hip": ["-ffp-contract=off"], "rvea_select.hip": ["-ffp-contract=off"], "rvea_small.hip": ["-ffp-contract=off"],
-              "bige_select.hip": ["-ffp-contract=off"], "tdea_select.hip": ["-ffp-contract=off"], "tdea_small.hip": ["-ffp-contract=off"],
+              "bige_select.hip": ["-ffp-contract=off"], "bige_small.hip": ["-ffp-contract=off"],
+              "tdea_select.hip": ["-ffp-contract=off"], "tdea_small.hip": ["-ffp-contract=off"],
               "nsga3_assoc.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "hv_exact.hip": ["-ffp-contract=off"], "hype_fitness.hip": ["-ffp-contract=off"],
               "rng.hip": ["-ffp-contract=fast-honor-pragmas"],
